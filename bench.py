@@ -22,10 +22,13 @@ any GPU call); under `python -m torch.distributed.run` it reads RANK / LOCAL_RAN
 512^2 image (SD-v1.5) + 5 s of audio (AudioLDM-L) + a 16-frame 320x576 video (zeroscope) through SpiderDecoder.generate,
 then the ONE gather of the padded outputs.
 
-One JSON line on rank 0, with `roofline` (dominant kernel = the decode weight-streaming GEMV, HBM-bound, timed live with HIP events IN
-THE CONDITION OF THE TIMED REGION -- beside the replaying decoder stream under `--schedule overlap` -- with the stand-alone figure next
-to it) and `cpu_baseline` (the fp32 CPU oracle timed on this box's host cores on a bounded sample); at N = 1 also one timed step of the
-any-to-many workload (`any2many`: configs[3]/[4], 8 prompts).
+One JSON line on rank 0. A plain run sets up, warms up, times the `--steps` steps and prints the headline (`value`, `ms_per_step`)
+with what the timed region recorded (`timed_steps`); `--dump-outputs DIR` also writes what the last timed step returned.
+`--full` adds everything measured beside it: serial / batched / precise-mode / other-decoder timings, `roofline` (dominant
+kernel = the decode weight-streaming GEMV, HBM-bound, timed live with HIP events IN THE CONDITION OF THE TIMED REGION -- beside the
+replaying decoder stream under `--schedule overlap` -- with the stand-alone figure next to it) and `cpu_baseline` (the fp32 CPU
+oracle timed on the host cores on a bounded sample); at N = 1 also one timed step of the any-to-many workload (`any2many`:
+configs[3]/[4], 8 prompts).
 """
 import argparse
 import json
@@ -68,7 +71,7 @@ def parse():
     p.add_argument("--denoise-steps", type=int, default=40)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--headline-only", action="store_true",
-                   help="timed region + roofline objects only (no serial / batched / other-decoder timings, no CPU baseline): the command "
+                   help="with --full: timed region + roofline objects only (no serial / batched / other-decoder timings, no CPU baseline): the command "
                         "the committed rocprofv3 summaries are taken from, so that their per-kernel averages are those of the timed region")
     p.add_argument("--schedule", default="overlap", choices=["overlap", "serial"],
                    help="text_image: overlap = response k's diffusion decoder on one stream beside response k+1's LLM pass on another "
@@ -89,6 +92,12 @@ def parse():
                    help="UNet residual stream in 16 bits instead of the fp32 master + 16-bit shadow the pipelines load by default")
     p.add_argument("--diffusion-dtype", default="f16", choices=["f16", "bf16"],
                    help="16-bit format of the UNet / text-encoder / VAE engines (f16 = the reference's torch_dtype)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, everything else the line reports: roofline objects, serial / batched / precise-mode / "
+                        "other-decoder timings, the any-to-many step and the CPU baseline (--headline-only / --no-extras / "
+                        "--no-any2many / --no-cpu-baseline trim this part). Without it the run is set-up, warm-up, timed steps, line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (rank 0's gathered outputs) as DIR/<name>.npy in float32")
     a = p.parse_args()
     global DIFF_DT
     DIFF_DT = torch.float16 if a.diffusion_dtype == "f16" else torch.bfloat16
@@ -254,6 +263,18 @@ class Responder:
         if "VIDEO" in self.TAGS:
             out["video"] = torch.from_numpy(np.stack([np.stack([np.asarray(f, dtype=np.uint8) for f in r.predictions["VIDEO"][0]]) for r in res])).to(self.dev)
         return out
+
+    def prime(self):
+        """Fill the empty `--schedule overlap` pipeline with the submits that finish no request yet -- what the first respond() would
+        do before its own step -- so that no step of the timed region carries them, also with --warmup 0."""
+        if self.args.schedule == "serial" or getattr(self.args, "serial_decoders", False) or self._B is not None:
+            return
+        B = self.args.batch
+        while self.infer.flush() is not None:
+            pass
+        self._B = B
+        for _ in range(self.infer.depth - 1):
+            assert self.infer.submit(inputs=self.request(B)) is None
 
     def respond_serial(self, batch=None):
         """One request start to finish on one stream (the latency of ONE request; the reference's schedule)."""
@@ -795,8 +816,8 @@ def llama8b_numbers(device):
 
 def run_timed(resp, args, rank, world, device):
     """The contract's timed region, shared by every workload (and driven on gloo with a stand-in responder by
-    tests/test_dp_gloo.py): W untimed warm-up steps, then EXACTLY K steps between barrier + device synchronize on both sides;
-    a step = this rank's responses + the ONE gather of their padded outputs to rank 0; time = MAX over ranks. Afterwards every
+    tests/test_dp_gloo.py): the pipeline primed (`Responder.prime`), W untimed warm-up steps, then EXACTLY K steps between barrier +
+    device synchronize on both sides; a step = this rank's responses + the ONE gather of their padded outputs to rank 0; time = MAX over ranks. Afterwards every
     rank leaves the process group, BEFORE rank 0's secondary timings and CPU baseline (tens of seconds), so that no rank waits in a
     collective on a slow host. Returns (seconds, rank 0's last gathered payload | None, {"world_size", "backend"})."""
     is_cuda = getattr(device, "type", "cpu") == "cuda"
@@ -809,6 +830,8 @@ def run_timed(resp, args, rank, world, device):
         return dp_mod().gather_padded(resp.respond(), args.batch, rank, world, dst=0)
 
     g = None
+    if hasattr(resp, "prime"):
+        resp.prime()
     for _ in range(args.warmup):
         g = one_step()
     if world > 1:
@@ -841,6 +864,24 @@ def run_timed(resp, args, rank, world, device):
 def dp_mod():
     from spider_amd import dp
     return dp
+
+
+DUMP_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(g, out_dir):
+    """`--dump-outputs DIR`: what the last timed step returned on rank 0 -- the gathered [world, batch, ...] generated token ids and
+    images (+ audio and video for any2many) -- as DIR/<name>.npy in float32, DUMP_BYTES at most in all. When the outputs are larger,
+    every array is cut to the same share of its elements at seeded positions (flat index order), the same positions in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {{"out": "image"}.get(k, k): v.cpu().numpy() for k, v in g.items() if k != "count"}
+    total = 4 * sum(a.size for a in arrs.values())
+    budget = DUMP_BYTES - 4096 * len(arrs)          # room for the .npy headers
+    for name, a in arrs.items():
+        if total > budget:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, a.size * budget // total, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(np.float32))
 
 
 def _dist4(xs):
@@ -890,6 +931,9 @@ def main():
         local = 0
     device = torch.device(f"cuda:{local}")
     torch.cuda.set_device(device)
+    # the pipelines draw each request's initial latents from the global generator, which torch seeds at random in every process:
+    # a fixed seed gives the same outputs for the same arguments
+    torch.manual_seed(2047 + rank)
     a2m = args.workload == "any2many"
     resp = AnyToManyResponder(args, device, rank) if a2m else Responder(args, device, rank)
 
@@ -905,6 +949,8 @@ def main():
         if g is not None:
             base["gathered"] = {k: list(v.shape) for k, v in g.items()}
             base["gather_bytes_per_rank"] = int(sum(v[0].numel() * v[0].element_size() for v in g.values()))
+        if args.dump_outputs:
+            dump_outputs(g, args.dump_outputs)
         if a2m:
             line = {"metric": "multimodal responses/sec (text->text+image+audio+video)", **base,
                     "config": {"workload": f"any-to-many (BASELINE configs[4]) through spider_amd.SpiderFreeInfer: {a.llm} text-decoder shapes, prompt {a.prompt_len} + {a.new_tokens} "
@@ -917,21 +963,27 @@ def main():
                     "rank0_stage_ms_last_step": {**resp.stage, **(resp.overlap_ms or {})}, "roofline": None, "cpu_baseline": None}
             print(json.dumps(line), flush=True)
         else:
-            roof = measure_roofline(resp, device)
             sched_depth = resp.infer.depth
-            extra = text_image_extras(args, resp, device)
-            if not args.no_extras and not args.headline_only and world == 1:
-                del resp
-                torch.cuda.empty_cache()
-                extra.update(other_decoders(device))
-                extra["llama3_8b"] = llama8b_numbers(device)
-                if not args.no_any2many:
-                    try:        # a secondary figure must never cost the headline line
-                        extra["any2many"] = any2many_extra(args, device)
-                    except Exception as e:      # noqa: BLE001
-                        extra["any2many"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-            cpu = None if (args.no_cpu_baseline or args.headline_only or world > 1) else cpu_baseline(args)   # reported at N=1 only
-            extra["roofline_response"] = response_roofline(args, extra, base["ms_per_step"])
+            # what the timed region itself recorded: no GPU work of its own
+            extra = {"_includes": resp.includes(), "timed_steps": step_statistics(resp)}   # per-step distribution, per-stream spans / idle
+            if resp.overlap_ms:
+                extra["overlap_last_step"] = resp.overlap_ms      # device time of the two concurrent passes of the last timed step
+            roof = cpu = None
+            if args.full:
+                roof = measure_roofline(resp, device)
+                extra.update(text_image_extras(args, resp, device))
+                if not args.no_extras and not args.headline_only and world == 1:
+                    del resp
+                    torch.cuda.empty_cache()
+                    extra.update(other_decoders(device))
+                    extra["llama3_8b"] = llama8b_numbers(device)
+                    if not args.no_any2many:
+                        try:        # a secondary figure must never cost the headline line
+                            extra["any2many"] = any2many_extra(args, device)
+                        except Exception as e:      # noqa: BLE001
+                            extra["any2many"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+                cpu = None if (args.no_cpu_baseline or args.headline_only or world > 1) else cpu_baseline(args)   # reported at N=1 only
+                extra["roofline_response"] = response_roofline(args, extra, base["ms_per_step"])
             line = {"metric": "multimodal responses/sec (text->text+image)", **base,
                     "config": {"workload": f"SpiderFree text->text+1x512^2 image through spider_amd.SpiderFreeInfer (qwen2.5omni_spider_web.py:458-521): "
                                            f"{args.llm} text-decoder shapes, prompt {a.prompt_len} + {a.new_tokens} greedy tokens, batch_decode, "
@@ -1009,14 +1061,11 @@ def response_roofline(args, extra, ms_per_step):
 
 
 def text_image_extras(args, resp, device):
-    """Secondary timings of the headline workload on rank 0 (outside the timed region)."""
+    """Secondary timings of the headline workload on rank 0 (outside the timed region; `--full`)."""
     from spider_amd import ops
     from spider_amd.unet import unet_flops, UNetConfig
     a = args
-    extra = {"_includes": resp.includes()}
-    extra["timed_steps"] = step_statistics(resp)              # per-step distribution + per-stream spans / idle time (medians)
-    if resp.overlap_ms:
-        extra["overlap_last_step"] = resp.overlap_ms      # device time of the two concurrent passes of the last timed step
+    extra = {}
     torch.cuda.synchronize(device)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     # UNet step ms (BASELINE.json's second metric): graph replay of one CFG-batch-2 evaluation

@@ -5,7 +5,7 @@
 import csv, glob, json, os, shutil, sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
-G, P = "gpurun_out", "profiles"
+G, P = sys.argv[2] if len(sys.argv) > 2 else "profiles_raw", "profiles"     # raw outputs of collect_profiles.sh, summaries
 os.makedirs(P, exist_ok=True)
 
 

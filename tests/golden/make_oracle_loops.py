@@ -14,7 +14,7 @@ its time budget on CPU work:
                            consistent-self-attention coins: inputs (latent, prompt states, pooled states, time ids) and the
                            fp32 latents after the loop, plus the latents after steps 1, 10 and 25.
 
-  oracle_loop_zeroscope40_f16.npz  zeroscope UNet3D (oracle.unet3d.UNet3DCfg.zeroscope(), weights random_unet3d_weights(seed=6)),
+  oracle_loop_zeroscope40_f16*.npz zeroscope UNet3D (oracle.unet3d.UNet3DCfg.zeroscope(), weights random_unet3d_weights(seed=6)),
                            CFG batch 2 on the [1, 4, 16, 40, 72] latent of configs[3] / [4], 40 DDIM steps, guidance 9.0
                            (spider_decoder.py:122-143, custom_vd.py:664-697): checksums of the seeded inputs and the fp32 latents after 1, 20, 40 steps.
 
@@ -142,10 +142,14 @@ def zeroscope_loop(frames=16, steps=40, guidance=9.0, keep=(1, 20)):
         if i + 1 in keep:
             kept[f"after_{i + 1}"] = x.numpy().copy()
         print(f"step {i + 1}/{steps} t={int(t)} |x|={float(x.norm()):.4f} ({time.time() - t0:.0f} s)", flush=True)
-    # (0.7 MB per latent tensor: the seeded inputs are not stored, only their checksums -- the test regenerates them)
-    np.savez_compressed(os.path.join(OUT, f"oracle_loop_zeroscope{steps}_f{frames}.npz"), latents_in_sum=float(lat.double().sum()),
-                        enc_sum=float(enc.double().sum()), latents_out=x.contiguous().numpy(), steps=steps, guidance=guidance,
-                        frames=frames, weights_seed=6, **kept)
+    # (0.7 MB per latent tensor: the seeded inputs are not stored, only their checksums -- the test regenerates them; the latents after
+    # step 1 go with the scalars, every later tensor into a file of its own, so that no fixture exceeds 1 MiB)
+    stem = os.path.join(OUT, f"oracle_loop_zeroscope{steps}_f{frames}")
+    later = {**{k: v for k, v in kept.items() if k != "after_1"}, "latents_out": x.contiguous().numpy()}
+    np.savez_compressed(f"{stem}.npz", latents_in_sum=float(lat.double().sum()), enc_sum=float(enc.double().sum()), steps=steps,
+                        guidance=guidance, frames=frames, weights_seed=6, after_1=kept["after_1"])
+    for k, v in later.items():
+        np.savez_compressed(f"{stem}_{k}.npz", **{k: v})
 
 
 def zeroscope8_inputs(frames=8):

@@ -71,3 +71,32 @@ def test_bench_two_ranks_any2many_share_one_gpu():
     assert g["tokens"] == [2, 2, 8] and g["image"] == [2, 2, 3, 512, 512] and g["audio"] == [2, 2, 80000] and g["video"] == [2, 2, 16, 320, 576, 3]
     assert g["count"] == [2] and d["value"] > 0
     assert set(d["rank0_stage_ms_last_step"]) >= {"image_decoder_ms", "audio_decoder_ms", "video_decoder_ms"}
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """a plain one-GPU run (no --full): exactly --steps timed steps also with --warmup 0 (the pipeline is primed outside them), none
+    of the --full measurements, and --dump-outputs writes what the last timed step returned -- the same in a second process"""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        out = tmp_path / str(run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--prompt-len", "192",
+               "--new-tokens", "12", "--denoise-steps", "5", "--dump-outputs", str(out)]
+        o = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=270, cwd=ROOT)
+        assert o.returncode == 0, o.stderr[-2000:]
+        lines = [l for l in o.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["warmup"] == 0 and d["timed_steps"]["step_wall_ms"]["n"] == 2
+        assert d["value"] > 0 and abs(d["value"] - 1 / (d["ms_per_step"] / 1e3)) < 1e-2 * d["value"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and "unet_step_ms" not in d and "serial_ms_per_response" not in d
+        assert sorted(os.listdir(out)) == ["image.npy", "tokens.npy"]
+        toks, img = np.load(out / "tokens.npy"), np.load(out / "image.npy")
+        assert toks.dtype == np.float32 and toks.shape == (1, 1, 12) and img.dtype == np.float32 and img.shape == (1, 1, 3, 512, 512)
+        assert (toks >= 0).all() and (toks == np.round(toks)).all() and 0 <= img.min() and img.max() <= 255
+        dumps.append((toks, img))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])      # same arguments, same outputs
