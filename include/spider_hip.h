@@ -62,6 +62,25 @@ int spider_decode_advance_i32(const int* next_ids, int* cur_ids, int* pos, int* 
 int spider_lm_head_argmax_bf16(const void* W, const void* x, const void* norm_w, float eps, int* out_ids, void* logits,
                                void* ws_val, void* ws_idx, int B, int V, int K, void* stream);
 
+/* Greedy decode with HF's deterministic logits processors (transformers generation/logits_process.py: RepetitionPenalty,
+ * SuppressTokens / single-token NoBadWords, MinLength / MinNewTokensLength; the reference passes repetition_penalty and
+ * min_length, spider.py:1471-1508, conversation.py:151-172). The *_proc forms of the two lm_head entry points apply, to the
+ * bf16-rounded logit widened to fp32 and before the arg-max:
+ *   bit n of seen[b] set: lv = lv < 0 ? lv * p : lv / p (IEEE fp32);  bit n of ban[b] set: -inf;
+ *   n one of the n_eos[0] (<= 8) ids of eos_ids while n_hist[b] < min_new[0]: -inf.
+ * Ties and an all -inf row go to the lowest id. logits (optional) stay the RAW bf16 logits. seen / ban: uint32 [B, ceil(V/32)];
+ * penalty float [1]; min_new, n_eos int32 [1]; eos_ids int32 [8]; n_hist int32 [B] -- all in device memory, read when the
+ * kernel runs (a captured graph serves requests with different values). */
+int spider_lm_head_argmax_proc_bf16(const void* W, const void* x, const void* norm_w, float eps, int* out_ids, void* logits,
+                                    void* ws_val, void* ws_idx, const void* seen, const void* ban, const float* penalty,
+                                    const int* min_new, const int* eos_ids, const int* n_eos, const int* n_hist, int B, int V,
+                                    int K, void* stream);
+/* spider_decode_advance_i32 + bit next_ids[b] of seen [B, ceil(V/32)] set (ids outside [0, V) set nothing) */
+int spider_decode_advance_seen_i32(const int* next_ids, int* cur_ids, int* pos, int* slot, int* kv_end, int* hist, int* n_hist,
+                                   void* seen, int V, int cap, int B, void* stream);
+/* bitmap [B, ceil(V/32)] |= the bits of ids [B, n] (int32); ids outside [0, V) are ignored, duplicates are harmless */
+int spider_token_bitmap_set_i32(const int* ids, void* bitmap, int B, int n, int V, void* stream);
+
 /* apply_rotary_pos_emb (modeling_llama3.py:150-183; modeling_llama.py:116-123) on q,k of a fused QKV
  * projection + KV-cache append (modeling_llama.py:190-193). qkv [B*S,(n_q+2n_kv)*d]; cos_sin fp32
  * [max_pos, d] = [cos(d/2) | sin(d/2)]; q_out [B*S,n_q,d]; caches [B,n_kv,T_max,d]. */
@@ -119,6 +138,11 @@ int spider_gemv_swiglu_fm_bf16(const void* Wfm_gate_up, const void* x, void* out
 /* logits (optional) [B, V] bf16; ws_val / ws_idx >= B * spider_lm_head_nparts(V) entries; ties -> lowest token id */
 int spider_lm_head_argmax_fm_bf16(const void* Wfm, const void* x, int* out_ids, void* logits, void* ws_val, void* ws_idx, int B,
                                   int V, int K, int fold_rmsnorm, float eps, void* stream);
+/* the fragment-major lm_head with the logits processors of spider_lm_head_argmax_proc_bf16 */
+int spider_lm_head_argmax_fm_proc_bf16(const void* Wfm, const void* x, int* out_ids, void* logits, void* ws_val, void* ws_idx,
+                                       const void* seen, const void* ban, const float* penalty, const int* min_new,
+                                       const int* eos_ids, const int* n_eos, const int* n_hist, int B, int V, int K,
+                                       int fold_rmsnorm, float eps, void* stream);
 
 /* ======================= MFMA GEMM / conv / attention ======================= */
 

@@ -5,14 +5,17 @@ batches of 1 ... 8 rows with ragged LEFT-padded prompts (1 ... 90 tokens), eager
 tests/test_llm_engine.py: ids must agree up to the first position where the oracle's own top-2 margin is below bf16 resolution; the
 step-0 logits must agree within the bf16 bounds. Not part of the suite; on the GPU box:
 
-    PYTHONPATH=. python scripts/fuzz_llm.py [cases] [seed]          # default 40 cases"""
+    PYTHONPATH=. python scripts/fuzz_llm.py [cases] [seed]          # default 40 cases
+    ... --processors    every case also decodes with randomly drawn logits processors (repetition_penalty, min_new_tokens / min_length,
+                        suppress_tokens, single-token bad_words_ids): graph == eager, and every token must be the lowest-index arg-max of
+                        the host restatement (llm.process_logits_host) on the engine's own raw logits and history. Off by default."""
 import random
 import sys
 
 import torch
 
 from oracle.llama import LlamaCfg, LlamaOracle
-from spider_amd.llm import LlamaEngine, LLMConfig
+from spider_amd.llm import LlamaEngine, LLMConfig, process_logits_host, resolve_logits_processors
 
 dev = torch.device("cuda:0")
 
@@ -94,7 +97,45 @@ def one_case(p, verbose=False):
                 if int(gen[0, t]) == int(ref_tok[0, t]) and float(top2[0] - top2[1]) >= max(0.08, 0.12 * float(ref_logits[0, t].abs().max())):
                     why = f"row 0 alone decodes {int(solo[0, t])} at step {t}, inside the batch {int(gen[0, t])} (healthy margin)"
                 break
+    if PROCESSORS and not why:
+        why = processed_case(eng, ids, am, S, T, vocab, random.Random(wseed))
     return desc, e, why
+
+
+PROCESSORS = "--processors" in sys.argv
+
+
+def processed_case(eng, ids, am, S, T, vocab, r):
+    """one processed request on the case's engine and prompt, replayed on the host from its raw logits"""
+    B = ids.shape[0]
+    eos = sorted({r.randrange(vocab) for _ in range(r.choice([0, 1, 3]))}) or None
+    kw = dict(repetition_penalty=r.choice([1.0, 1.05, 1.3, 2.0, 0.8]), suppress_tokens=[r.randrange(vocab) for _ in range(r.choice([0, 2, 40]))],
+              bad_words_ids=[[r.randrange(vocab)] for _ in range(r.choice([0, 1]))])
+    kw.update(r.choice([dict(min_new_tokens=r.randint(0, T)), dict(min_length=max(0, S + r.randint(-2, T))), {}]))
+    embeds = r.random() < 0.5
+    inp = dict(inputs_embeds=eng.embed_tokens(ids)) if embeds else dict(input_ids=ids)
+    outs = []
+    for use_graph in (False, True):
+        o = eng.generate(**inp, attention_mask=am, max_new_tokens=T, eos_token_id=eos if eos else [], pad_token_id=0,
+                         return_dict_in_generate=True, return_logits=True, use_graph=use_graph, **kw)
+        n = o.logits.shape[1]
+        outs.append((o.sequences[:, -n:].cpu(), o.logits.float().cpu()))
+    if not all(torch.equal(a, b) for a, b in zip(*outs)):
+        return f"processed ({kw}): graph decode and eager decode disagree"
+    gen, lg = outs[0]
+    pen, min_new, ban = resolve_logits_processors(S, eos, **kw)
+    seen = torch.zeros(B, vocab, dtype=torch.bool)
+    if not embeds:
+        seen.scatter_(1, ids, True)
+    alive = torch.ones(B, dtype=torch.bool)
+    for t in range(gen.shape[1]):
+        want = process_logits_host(lg[:, t], seen, pen, ban, eos, t, min_new).argmax(-1)
+        if bool((alive & (want != gen[:, t])).any()):
+            return f"processed ({kw}, eos {eos}, {'embeds' if embeds else 'ids'}): step {t} tokens {gen[:, t].tolist()} vs host replay {want.tolist()}"
+        seen.scatter_(1, gen[:, t:t + 1], True)
+        if eos:
+            alive &= ~torch.isin(gen[:, t], torch.tensor(eos))
+    return ""
 
 
 def main():

@@ -6,6 +6,8 @@
 //   RoPE + KV append   spider/models/modeling_llama3.py:128-183  (old: modeling_llama.py:77-123,190-193)
 //   decode attention   spider/models/modeling_llama3.py:202-237  (repeat_kv + eager softmax in fp32)
 //   lm_head + argmax   spider/models/modeling_llama3.py:870-871 + HF greedy loop (spider.py:1492-1508)
+//   logits processors  transformers' RepetitionPenalty / SuppressTokens / NoBadWords (single token) / MinLength, which the callers'
+//                      repetition_penalty / min_length reach (spider.py:1471-1508): PROC forms of the two lm_head kernels
 //
 // Layouts: activations [B, H] bf16 row-major; weights [N, K] bf16 row-major (nn.Linear layout, never
 // transposed); KV cache [B, n_kv, T_max, d] bf16. All reductions accumulate in fp32.
@@ -314,11 +316,51 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
 // reference's bf16 lm_head output is), keeps its best (value, lowest index); each block writes one
 // partial. Stage 2: one block reduces the partials per batch row. Ties -> lowest token id.
 // ----------------------------------------------------------------------------------------------
-template <int NB, int R>
+//
+// PROC forms (spider_lm_head_argmax_proc_bf16 / _fm_proc_bf16): HF's deterministic logits processors in the arg-max epilogue,
+// applied to the bf16-rounded logit widened to fp32 -- the value transformers hands to its processors
+// (generation/logits_process.py: RepetitionPenalty, NoBadWords / SuppressTokens, MinLength / MinNewTokensLength):
+//   bit n of seen[b] set:          lv = lv < 0 ? lv * p : lv / p     (fp32, IEEE division)
+//   bit n of ban[b] set:           lv = -inf
+//   n an EOS id, n_hist[b] < min_new:  lv = -inf
+// Every parameter lives in device memory (one captured decode graph serves requests with different values); the bitmaps are
+// uint32 [B, words], words = ceil(V / 32), read with per-lane (vector) loads. The optional logits output stays the RAW logit.
+struct LmProc {
+    const uint32_t* seen;     // [B, words] ids already in the row's sequence (prompt ids of an input_ids call + generated ids)
+    const uint32_t* ban;      // [B, words] suppress_tokens / single-token bad_words_ids
+    const float* penalty;     // [1]
+    const int* min_new;       // [1] EOS is banned while n_hist[b] < min_new
+    const int* eos_ids;       // [8]
+    const int* n_eos;         // [1] 0 ... 8
+    const int* n_hist;        // [B] tokens generated so far
+    int words;
+};
+
+// bit 0: row n of sequence b is in `seen`; bit 1: it is banned (ban bitmap, or an EOS id before min_new tokens)
+__device__ __forceinline__ uint32_t lm_proc_flags(const LmProc& pr, int b, int n) {
+    const size_t w = (size_t)b * pr.words + (n >> 5);
+    const uint32_t bit = 1u << (n & 31);
+    uint32_t f = (pr.seen[w] & bit) ? 1u : 0u;
+    if (pr.ban[w] & bit) f |= 2u;
+    if (pr.n_hist[b] < pr.min_new[0]) {
+        const int ne = min(pr.n_eos[0], 8);
+        for (int e = 0; e < ne; ++e)
+            if (pr.eos_ids[e] == n) f |= 2u;
+    }
+    return f;
+}
+
+__device__ __forceinline__ float lm_proc_apply(float lv, uint32_t flags, float p) {
+    if (flags & 1u) lv = lv < 0.f ? lv * p : __fdiv_rn(lv, p);
+    if (flags & 2u) lv = -INFINITY;
+    return lv;
+}
+
+template <int NB, int R, bool PROC = false>
 __global__ __launch_bounds__(256) void lmhead_partial_kernel(const bf16_t* __restrict__ W, const bf16_t* __restrict__ x,
                                                              const bf16_t* __restrict__ norm_w, float eps,
                                                              float* __restrict__ pval, int* __restrict__ pidx,
-                                                             bf16_t* __restrict__ logits, int V, int K) {
+                                                             bf16_t* __restrict__ logits, int V, int K, LmProc pr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* xs = reinterpret_cast<bf16_t*>(smem);
     __shared__ float red[4];
@@ -395,16 +437,24 @@ __global__ __launch_bounds__(256) void lmhead_partial_kernel(const bf16_t* __res
                 }
             }
         }
+        uint32_t pflags = 0;    // PROC: lane b * R + r holds the flags of (sequence b, row n0 + r), loaded per lane
+        float pen = 1.f;
+        if (PROC) {
+            if (lane < NB * R && n0 + lane % R < rend) pflags = lm_proc_flags(pr, lane / R, n0 + lane % R);
+            pen = pr.penalty[0];
+        }
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const float s = wave_sum(acc[b][r]);
                 const int n = n0 + r;
+                const uint32_t fl = PROC ? (uint32_t)__shfl((int)pflags, b * R + r, 64) : 0u;
                 if (n < rend) {
                     const bf16_t lb = f32_to_bf16(s);
-                    const float lv = bf16_to_f32(lb);
+                    float lv = bf16_to_f32(lb);
                     if (logits && lane == 0) logits[(size_t)b * V + n] = lb;
+                    if (PROC) lv = lm_proc_apply(lv, fl, pen);
                     if (lv > best[b] || (lv == best[b] && n < besti[b])) { best[b] = lv; besti[b] = n; }
                 }
             }
@@ -473,6 +523,39 @@ __global__ void decode_advance_kernel(const int* __restrict__ next_ids, int* __r
         if (n < cap) hist[(size_t)b * cap + n] = id;
         n_hist[b] = n + 1;
     }
+}
+
+// decode_advance for the processed greedy path: the same bookkeeping, and the chosen id's bit is set in the sequence's row of
+// the `seen` bitmap [B, words] (one thread per row owns the row: a plain read-modify-write). Ids outside [0, V) set nothing.
+__global__ void decode_advance_seen_kernel(const int* __restrict__ next_ids, int* __restrict__ cur_ids, int* __restrict__ pos,
+                                           int* __restrict__ slot, int* __restrict__ kv_end, int* __restrict__ hist,
+                                           int* __restrict__ n_hist, uint32_t* __restrict__ seen, int V, int cap, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int id = next_ids[b];
+    cur_ids[b] = id;
+    pos[b] += 1;
+    slot[b] += 1;
+    kv_end[b] += 1;
+    if (hist) {
+        const int n = n_hist[b];
+        if (n < cap) hist[(size_t)b * cap + n] = id;
+        n_hist[b] = n + 1;
+    }
+    if (id >= 0 && id < V) {
+        const size_t w = (size_t)b * ((V + 31) / 32) + (id >> 5);
+        seen[w] = seen[w] | (1u << (id & 31));
+    }
+}
+
+// bitmap[b, id / 32] |= 1 << (id % 32) for every id of ids [B, n] that lies in [0, V); duplicates are harmless (atomicOr)
+__global__ __launch_bounds__(256) void token_bitmap_set_kernel(const int* __restrict__ ids, uint32_t* __restrict__ bitmap,
+                                                               int B, int n, int V) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * n) return;
+    const int b = (int)(i / n);
+    const int id = ids[i];
+    if (id >= 0 && id < V) atomicOr(bitmap + (size_t)b * ((V + 31) / 32) + (id >> 5), 1u << (id & 31));
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1119,12 +1202,13 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_kernel(const bf16_t* __re
 // NORM: x is the UN-normalised residual stream and Wfm was built from W * diag(norm_w): the kernel accumulates sum x^2 of
 // every sequence from the x fragments it streams anyway and applies rsqrt(mean + eps) to the accumulators (RMSNorm folded
 // into the projection: no rmsnorm launch, no normalised copy of x).
-template <int MODE, int NW, bool NORM>
+// PROC (MODE 2 only): the logits processors of LmProc in the arg-max epilogue (see lmhead_partial_kernel).
+template <int MODE, int NW, bool NORM, bool PROC = false>
 __global__ __launch_bounds__(NW * 64) void skinny_fm_kernel(const bf16_t* __restrict__ Wfm, const bf16_t* __restrict__ x,
                                                             bf16_t* __restrict__ out, const bf16_t* __restrict__ bias,
                                                             const bf16_t* __restrict__ res, float* __restrict__ pval,
                                                             int* __restrict__ pidx, int B, int N, int K, int NG,
-                                                            uint32_t w_bytes, uint32_t x_bytes, float eps) {
+                                                            uint32_t w_bytes, uint32_t x_bytes, float eps, LmProc pr) {
     constexpr bool GATEUP = MODE == 1;
     constexpr int TN = GATEUP ? 2 : 1;
     constexpr int D = 2;
@@ -1218,14 +1302,36 @@ __global__ __launch_bounds__(NW * 64) void skinny_fm_kernel(const bf16_t* __rest
             if (MODE == 2) {
                 float lb = -INFINITY;
                 int li = 0x7fffffff;
+                uint32_t sw = 0, bw = 0;    // PROC: the lane's 4 rows share one bitmap word (16 rg + 4 g is a multiple of 4)
+                float pen = 1.f;
+                bool no_eos = false;
+                if (PROC) {
+                    const int nn0 = 16 * rg + 4 * g;
+                    if (nn0 < N && m < B) {
+                        const size_t w = (size_t)m * pr.words + (nn0 >> 5);
+                        sw = pr.seen[w] >> (nn0 & 31);
+                        bw = pr.ban[w] >> (nn0 & 31);
+                        no_eos = pr.n_hist[m] < pr.min_new[0];
+                    }
+                    pen = pr.penalty[0];
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int nn = 16 * rg + 4 * g + j;
                     const bf16_t q = f32_to_bf16(v[0][j]);
-                    const float lv = bf16_to_f32(q);
+                    float lv = bf16_to_f32(q);
                     if (nn < N && m < B) {
                         if (out) out[(size_t)m * N + nn] = q;
-                        if (lv > lb) { lb = lv; li = nn; }        // j ascending: the first maximum has the lowest index
+                        if (PROC) {
+                            uint32_t fl = ((sw >> j) & 1u) | (((bw >> j) & 1u) << 1);
+                            if (no_eos) {
+                                const int ne = min(pr.n_eos[0], 8);
+                                for (int e = 0; e < ne; ++e)
+                                    if (pr.eos_ids[e] == nn) fl |= 2u;
+                            }
+                            lv = lm_proc_apply(lv, fl, pen);
+                            if (lv > lb || (lv == lb && nn < li)) { lb = lv; li = nn; }   // a row of -inf only still yields its lowest id
+                        } else if (lv > lb) { lb = lv; li = nn; }        // j ascending: the first maximum has the lowest index
                     }
                 }
 #pragma unroll
@@ -1399,7 +1505,11 @@ int spider_gemv_swiglu_bf16(const void* W_gate_up, const void* x, void* out, con
 #define LMHEAD_LAUNCH(NB_)                                                                                     \
     lmhead_partial_kernel<NB_, 2><<<nparts, 256, (size_t)NB_ * K * 2, (hipStream_t)stream>>>(                   \
         (const bf16_t*)W, (const bf16_t*)x, (const bf16_t*)norm_w, eps, (float*)ws_val, (int*)ws_idx,          \
-        (bf16_t*)logits, V, K)
+        (bf16_t*)logits, V, K, LmProc{})
+#define LMHEAD_PROC_LAUNCH(NB_)                                                                                \
+    lmhead_partial_kernel<NB_, 2, true><<<nparts, 256, (size_t)NB_ * K * 2, (hipStream_t)stream>>>(             \
+        (const bf16_t*)W, (const bf16_t*)x, (const bf16_t*)norm_w, eps, (float*)ws_val, (int*)ws_idx,          \
+        (bf16_t*)logits, V, K, pr)
 
 // cur_ids <- next_ids; pos, slot, kv_end += 1; hist[b, n_hist[b]++] = next_ids[b] (hist / n_hist may be NULL). All int32 [B].
 int spider_decode_advance_i32(const int* next_ids, int* cur_ids, int* pos, int* slot, int* kv_end, int* hist, int* n_hist,
@@ -1408,6 +1518,35 @@ int spider_decode_advance_i32(const int* next_ids, int* cur_ids, int* pos, int* 
     SPIDER_CHECK(!hist || (n_hist && cap > 0), "decode_advance: history needs its counters and capacity");
     decode_advance_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(next_ids, cur_ids, pos, slot, kv_end, hist, n_hist, cap, B);
     SPIDER_LAUNCH_OK();
+    return 0;
+}
+
+// decode_advance + bit next_ids[b] of seen [B, ceil(V/32)] set (processed greedy path)
+int spider_decode_advance_seen_i32(const int* next_ids, int* cur_ids, int* pos, int* slot, int* kv_end, int* hist, int* n_hist,
+                                   void* seen, int V, int cap, int B, void* stream) {
+    SPIDER_CHECK(next_ids && cur_ids && pos && slot && kv_end && B > 0, "decode_advance_seen: cursors required");
+    SPIDER_CHECK(!hist || (n_hist && cap > 0), "decode_advance_seen: history needs its counters and capacity");
+    SPIDER_CHECK(seen && V > 0, "decode_advance_seen: bitmap and vocabulary size required");
+    decode_advance_seen_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(next_ids, cur_ids, pos, slot, kv_end, hist, n_hist,
+                                                                            (uint32_t*)seen, V, cap, B);
+    SPIDER_LAUNCH_OK();
+    return 0;
+}
+
+// ids int32 [B, n] -> bitmap uint32 [B, ceil(V/32)] |= bits of the row's ids; ids outside [0, V) are ignored
+int spider_token_bitmap_set_i32(const int* ids, void* bitmap, int B, int n, int V, void* stream) {
+    SPIDER_CHECK(ids && bitmap && B > 0 && n > 0 && V > 0, "token_bitmap_set: ids [B, n], bitmap and V > 0 required");
+    const long total = (long)B * n;
+    token_bitmap_set_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(ids, (uint32_t*)bitmap, B, n, V);
+    SPIDER_LAUNCH_OK();
+    return 0;
+}
+
+static int lm_proc_make(LmProc& pr, const void* seen, const void* ban, const float* penalty, const int* min_new,
+                        const int* eos_ids, const int* n_eos, const int* n_hist, int V) {
+    SPIDER_CHECK(seen && ban && penalty && min_new && eos_ids && n_eos && n_hist,
+                 "lm_head_argmax_proc: seen, ban, penalty, min_new, eos_ids, n_eos and n_hist are required");
+    pr = LmProc{(const uint32_t*)seen, (const uint32_t*)ban, penalty, min_new, eos_ids, n_eos, n_hist, (V + 31) / 32};
     return 0;
 }
 
@@ -1437,6 +1576,32 @@ int spider_lm_head_argmax_bf16(const void* W, const void* x, const void* norm_w,
     return 0;
 }
 
+// spider_lm_head_argmax_bf16 with the logits processors of LmProc in the arg-max epilogue; logits stay the raw bf16 logits
+int spider_lm_head_argmax_proc_bf16(const void* W, const void* x, const void* norm_w, float eps, int* out_ids, void* logits,
+                                    void* ws_val, void* ws_idx, const void* seen, const void* ban, const float* penalty,
+                                    const int* min_new, const int* eos_ids, const int* n_eos, const int* n_hist, int B, int V,
+                                    int K, void* stream) {
+    SPIDER_CHECK(B >= 1 && B <= 8, "lm_head_argmax_proc: batch must be 1..8");
+    SPIDER_CHECK(V > 0 && K > 0 && K % 8 == 0 && (size_t)B * K * 2 <= 64 * 1024, "lm_head_argmax_proc: bad K");
+    LmProc pr;
+    if (lm_proc_make(pr, seen, ban, penalty, min_new, eos_ids, n_eos, n_hist, V)) return -1;
+    const int nparts = spider_lm_head_nparts(V);
+    switch (B) {
+        case 1: LMHEAD_PROC_LAUNCH(1); break;
+        case 2: LMHEAD_PROC_LAUNCH(2); break;
+        case 3: LMHEAD_PROC_LAUNCH(3); break;
+        case 4: LMHEAD_PROC_LAUNCH(4); break;
+        case 5: LMHEAD_PROC_LAUNCH(5); break;
+        case 6: LMHEAD_PROC_LAUNCH(6); break;
+        case 7: LMHEAD_PROC_LAUNCH(7); break;
+        default: LMHEAD_PROC_LAUNCH(8); break;
+    }
+    SPIDER_LAUNCH_OK();
+    argmax_final_kernel<<<B, 256, 0, (hipStream_t)stream>>>((const float*)ws_val, (const int*)ws_idx, out_ids, nparts);
+    SPIDER_LAUNCH_OK();
+    return 0;
+}
+
 // Fragment-major forms (see skinny_fm_kernel): Wfm is the repacked copy of W [N, K] (K % 64 == 0; rows padded to a multiple
 // of 16 with zeros; the gate/up form packs [gate | up] with I % 16 == 0). 1 <= B <= 16. fold_rmsnorm = 0: x is used as is;
 // 1: x is the un-normalised residual stream, Wfm was repacked from W * diag(norm_w), and the kernel applies
@@ -1448,7 +1613,7 @@ int spider_gemv_fm_bf16(const void* Wfm, const void* x, void* out, const void* b
     const size_t wb = (size_t)NG * 16 * K * 2, xb = (size_t)B * K * 2;
     SPIDER_CHECK(wb < ((size_t)1 << 32), "gemv_fm: weight copy must be < 4 GiB");
 #define FM_ARGS(OUT_, BIAS_, RES_, PV_, PI_, N_) (const bf16_t*)Wfm, (const bf16_t*)x, (bf16_t*)(OUT_), (const bf16_t*)(BIAS_), (const bf16_t*)(RES_), \
-        (float*)(PV_), (int*)(PI_), B, N_, K, NG, (uint32_t)wb, (uint32_t)xb, eps
+        (float*)(PV_), (int*)(PI_), B, N_, K, NG, (uint32_t)wb, (uint32_t)xb, eps, LmProc{}
     if (fold_rmsnorm) skinny_fm_kernel<0, 8, true><<<NG, 512, 0, (hipStream_t)stream>>>(FM_ARGS(out, bias, res, nullptr, nullptr, N));
     else skinny_fm_kernel<0, 8, false><<<NG, 512, 0, (hipStream_t)stream>>>(FM_ARGS(out, bias, res, nullptr, nullptr, N));
     SPIDER_LAUNCH_OK();
@@ -1480,7 +1645,31 @@ int spider_lm_head_argmax_fm_bf16(const void* Wfm, const void* x, int* out_ids, 
     if (nparts > NG) nparts = NG;
     if (fold_rmsnorm) skinny_fm_kernel<2, 8, true><<<nparts, 512, 0, (hipStream_t)stream>>>(FM_ARGS(logits, nullptr, nullptr, ws_val, ws_idx, V));
     else skinny_fm_kernel<2, 8, false><<<nparts, 512, 0, (hipStream_t)stream>>>(FM_ARGS(logits, nullptr, nullptr, ws_val, ws_idx, V));
+    SPIDER_LAUNCH_OK();
+    argmax_final_kernel<<<B, 256, 0, (hipStream_t)stream>>>((const float*)ws_val, (const int*)ws_idx, out_ids, nparts);
+    SPIDER_LAUNCH_OK();
+    return 0;
+}
 #undef FM_ARGS
+
+// spider_lm_head_argmax_fm_bf16 with the logits processors of LmProc in the arg-max epilogue; logits stay the raw bf16 logits
+int spider_lm_head_argmax_fm_proc_bf16(const void* Wfm, const void* x, int* out_ids, void* logits, void* ws_val, void* ws_idx,
+                                       const void* seen, const void* ban, const float* penalty, const int* min_new,
+                                       const int* eos_ids, const int* n_eos, const int* n_hist, int B, int V, int K,
+                                       int fold_rmsnorm, float eps, void* stream) {
+    SPIDER_CHECK(B >= 1 && B <= 16 && V > 0 && K > 0 && K % 64 == 0, "lm_head_argmax_fm_proc: 1 <= B <= 16, K a positive multiple of 64");
+    const int NG = (V + 15) / 16;
+    const size_t wb = (size_t)NG * 16 * K * 2, xb = (size_t)B * K * 2;
+    SPIDER_CHECK(wb < ((size_t)1 << 32), "lm_head_argmax_fm_proc: weight copy must be < 4 GiB");
+    LmProc pr;
+    if (lm_proc_make(pr, seen, ban, penalty, min_new, eos_ids, n_eos, n_hist, V)) return -1;
+    int nparts = spider_lm_head_nparts(V);
+    if (nparts > NG) nparts = NG;
+#define FM_PROC_ARGS (const bf16_t*)Wfm, (const bf16_t*)x, (bf16_t*)logits, (const bf16_t*)nullptr, (const bf16_t*)nullptr, \
+        (float*)ws_val, (int*)ws_idx, B, V, K, NG, (uint32_t)wb, (uint32_t)xb, eps, pr
+    if (fold_rmsnorm) skinny_fm_kernel<2, 8, true, true><<<nparts, 512, 0, (hipStream_t)stream>>>(FM_PROC_ARGS);
+    else skinny_fm_kernel<2, 8, false, true><<<nparts, 512, 0, (hipStream_t)stream>>>(FM_PROC_ARGS);
+#undef FM_PROC_ARGS
     SPIDER_LAUNCH_OK();
     argmax_final_kernel<<<B, 256, 0, (hipStream_t)stream>>>((const float*)ws_val, (const int*)ws_idx, out_ids, nparts);
     SPIDER_LAUNCH_OK();

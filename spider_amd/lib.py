@@ -35,9 +35,13 @@ SIGNATURES = {
     "spider_lm_head_nparts": (_i, [_i]),
     "spider_decode_advance_i32": (_i, [_vp] * 7 + [_i, _i, _vp]),
     "spider_lm_head_argmax_bf16": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "spider_lm_head_argmax_proc_bf16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 11 + [_i, _i, _i, _vp]),
+    "spider_decode_advance_seen_i32": (_i, [_vp] * 8 + [_i, _i, _i, _vp]),
+    "spider_token_bitmap_set_i32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "spider_gemv_fm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "spider_gemv_swiglu_fm_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "spider_lm_head_argmax_fm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "spider_lm_head_argmax_fm_proc_bf16": (_i, [_vp] * 13 + [_i, _i, _i, _i, _f, _vp]),
     "spider_rope_kv_append_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "spider_rope_kv_append_mrope_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "spider_attn_decode_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),

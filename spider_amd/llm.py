@@ -16,6 +16,10 @@ Data layout in HBM (per engine):
     w_down [H, I], ln1 [H], ln2 [H] | norm [H] | lm_head [V, H]
     KV cache: 2 x [L, B_max, n_kv, T_max, d] bf16, preallocated once; rope table [max_pos, d] fp32.
 Decode = 5 weight-streaming launches per layer (+1 tiny split-KV combine), captured in a hipGraph.
+
+Logits processors (opt-in keywords of generate: repetition_penalty, min_length / min_new_tokens, suppress_tokens, single-token
+bad_words_ids -- what spider.py:1471-1508 and conversation.py:151-172 forward to HF's generate) run in the arg-max epilogue of the
+lm_head kernels on per-sequence token bitmaps kept in the decode state; neutral values use the unprocessed kernels and graph.
 """
 from __future__ import annotations
 
@@ -121,6 +125,62 @@ def _id_list(v) -> Optional[List[int]]:
     if v is None:
         return None
     return [int(v)] if isinstance(v, int) else [int(x) for x in v]
+
+
+MAX_EOS_IDS = 8     # EOS ids the min-length processor of the lm_head kernels compares against
+
+
+def resolve_logits_processors(prompt_len: int, eos: Optional[List[int]], repetition_penalty=1.0, min_length=0, min_new_tokens=0,
+                              suppress_tokens=None, bad_words_ids=None):
+    """The deterministic logits processors of transformers' `generate` (GenerationMixin._get_logits_processor), resolved on the
+    host to what the lm_head kernels take: (penalty p, min_new, sorted ban list).
+      * repetition_penalty: RepetitionPenaltyLogitsProcessor is built for any value other than 1 and insists on a float > 0.
+      * min_new = number of generated tokens before which EOS is banned. min_new_tokens > 0 wins (HF sets min_length from it);
+        otherwise min_length counts the prompt: max(0, min_length - prompt_len), in both input modes (with inputs_embeds only
+        HF reduces min_length by the prompt length, _prepare_generated_length). No EOS id: both are no-ops.
+      * suppress_tokens and single-token bad_words_ids are one ban set; NoBadWordsLogitsProcessor drops entries equal to [eos].
+        A multi-token bad word depends on the previous tokens and is not implemented."""
+    p = 1.0
+    if repetition_penalty is not None and repetition_penalty != 1.0:
+        if not isinstance(repetition_penalty, float) or not (repetition_penalty > 0):
+            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty}")
+        p = repetition_penalty
+    for name, v in (("min_length", min_length), ("min_new_tokens", min_new_tokens)):
+        if v is not None and (not isinstance(v, int) or v < 0):
+            raise ValueError(f"`{name}` has to be a non-negative integer, but is {v}")
+    min_new = 0
+    if eos:
+        if len(eos) > MAX_EOS_IDS:
+            raise ValueError(f"at most {MAX_EOS_IDS} eos_token_id values are supported with min_length / min_new_tokens")
+        min_new = int(min_new_tokens) if min_new_tokens else max(0, int(min_length or 0) - int(prompt_len))
+    ban = set(int(t) for t in (suppress_tokens if suppress_tokens is not None else ()))
+    for w in (bad_words_ids or ()):
+        w = [int(t) for t in w]
+        if len(w) != 1:
+            raise NotImplementedError(f"bad_words_ids entry {w}: only single-token bad words are supported "
+                                      "(a multi-token entry bans its last token only after its prefix)")
+        if not (eos and w[0] in eos):
+            ban.add(w[0])
+    return p, min_new, sorted(ban)
+
+
+def process_logits_host(logits: torch.Tensor, seen: torch.Tensor, p: float, ban: Sequence[int], eos: Optional[List[int]],
+                        n_new: int, min_new: int) -> torch.Tensor:
+    """Host restatement of the lm_head kernels' epilogue, in fp32, on raw logits [B, V]: `seen` [B, V] bool marks the ids the
+    repetition penalty applies to (every id of the row's input_ids, pads included, plus the generated ids; the generated ids alone
+    for an inputs_embeds call), `n_new` = tokens generated so far. The greedy token is the lowest-index arg-max of the result."""
+    lv = logits.float().clone()
+    if p != 1.0:
+        lv = torch.where(seen, torch.where(lv < 0, lv * p, lv / p), lv)
+    V = lv.shape[-1]
+    for t in ban:
+        if 0 <= t < V:
+            lv[:, t] = -math.inf
+    if eos and n_new < min_new:
+        for t in eos:
+            if 0 <= t < V:
+                lv[:, t] = -math.inf
+    return lv
 
 
 def finalize_greedy(tokens: torch.Tensor, eos: Optional[List[int]], pad: Optional[int], stopping_criteria,
@@ -340,9 +400,17 @@ class LlamaEngine:
             w[first_row:first_row + rows.shape[0]] = rows.to(device=w.device, dtype=w.dtype)
         self._vocab_changed()
 
-    def would_capture(self, B: int, output_hidden_states: bool = False, return_logits: bool = False, cache_set: int = 0) -> bool:
-        """True when the decode loop of such a request would capture its hipGraph (state missing or not captured yet)"""
-        ent = self._graphs.get((int(B), bool(output_hidden_states), bool(return_logits), int(cache_set)))
+    @staticmethod
+    def _state_key(B: int, output_hidden_states: bool, return_logits: bool, cache_set: int, processed: bool = False) -> tuple:
+        """key of a decode state + captured graph; requests with logits processors have their own (one more element)"""
+        key = (int(B), bool(output_hidden_states), bool(return_logits), int(cache_set))
+        return key + (True,) if processed else key
+
+    def would_capture(self, B: int, output_hidden_states: bool = False, return_logits: bool = False, cache_set: int = 0,
+                      processed: bool = False) -> bool:
+        """True when the decode loop of such a request would capture its hipGraph (state missing or not captured yet).
+        processed: a request with non-neutral logits processors (repetition_penalty != 1, a ban set, or EOS banned at first)"""
+        ent = self._graphs.get(self._state_key(B, output_hidden_states, return_logits, cache_set, processed))
         return ent is None or ent[1] is None
 
     def _vocab_changed(self):
@@ -417,7 +485,14 @@ class LlamaEngine:
                 h = ops.gemv(lw["w_down"], st["act"], res=h1, out=st["h2"][l & 1])
             if hs is not None:
                 hs[l + 1].copy_(h)
-        if fm:
+        proc = st.get("proc")      # logits processors in the arg-max epilogue (their parameters are read from the state's buffers)
+        if proc is not None and fm:
+            ops.lm_head_argmax_fm_proc(self.lm_head_fm, h, c.vocab, proc, out_ids=st["next_ids"], ws=st["lm_ws"],
+                                       logits=st.get("logits"), norm_eps=c.eps)
+        elif proc is not None:
+            ops.lm_head_argmax_proc(self.lm_head, h, proc, norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"], ws=st["lm_ws"],
+                                    logits=st.get("logits"))
+        elif fm:
             ops.lm_head_argmax_fm(self.lm_head_fm, h, c.vocab, out_ids=st["next_ids"], ws=st["lm_ws"], logits=st.get("logits"),
                                   norm_eps=c.eps)
         else:
@@ -426,9 +501,15 @@ class LlamaEngine:
         if hs is not None:  # HF reports the normed state as the last hidden state (modeling_llama3.py:619-623)
             ops.rmsnorm(h, self.norm, c.eps, out=hs[c.layers])
         # advance the device-side cursors and append the token to the on-device history (index math only, one launch)
-        ops.decode_advance(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["hist"], st["n_hist"])
+        if proc is not None:    # ... and the token joins the sequence's `seen` set before the next step's lm_head
+            ops.decode_advance_seen(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["seen"], c.vocab,
+                                    st["hist"], st["n_hist"])
+        else:
+            ops.decode_advance(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["hist"], st["n_hist"])
 
-    def _make_state(self, B: int, want_hidden: bool, want_logits: bool, cache_set: int = 0) -> dict:
+    _PROC_BUFS = ("seen", "ban", "penalty", "min_new", "eos_ids", "n_eos")
+
+    def _make_state(self, B: int, want_hidden: bool, want_logits: bool, cache_set: int = 0, processed: bool = False) -> dict:
         c, dv = self.cfg, self.device
         nq_d = c.n_q * c.head_dim
         # one split-KV block per CU (256): measured on Qwen-7B shapes at T~1.6k: 2.93 / 2.90 / 3.14 ms per token at 32 / 64 / 96 splits
@@ -449,6 +530,11 @@ class LlamaEngine:
             st["hidden_buf"] = bf(c.layers + 1, B, c.hidden)
         if want_logits:
             st["logits"] = bf(B, c.vocab)
+        if processed:   # token bitmaps (uint32 words kept as int32) and the processors' parameters, all read by the kernels at run time
+            W = ops.bitmap_words(c.vocab)
+            st.update(seen=i32(B, W), ban=i32(B, W), penalty=torch.ones(1, dtype=torch.float32, device=dv), min_new=i32(1),
+                      eos_ids=i32(MAX_EOS_IDS), n_eos=i32(1))
+            st["proc"] = {k: st[k] for k in self._PROC_BUFS + ("n_hist",)}
         return st
 
     # ------------------------------------------------------------------ public generate
@@ -465,7 +551,8 @@ class LlamaEngine:
                       output_hidden_states: bool = False, return_dict_in_generate: bool = False,
                       num_beams: int = 1, do_sample: bool = False, use_cache: bool = True, output_attentions: bool = False,
                       use_graph: bool = True, sync_every: int = 1, return_logits: bool = False,
-                      position_ids: Optional[torch.Tensor] = None, cache_set: int = 0, **unused):
+                      position_ids: Optional[torch.Tensor] = None, cache_set: int = 0, repetition_penalty=1.0, min_length=0,
+                      min_new_tokens=0, suppress_tokens=None, bad_words_ids=None, **unused):
         """First half of `generate`: the prompt pass (KV cache of `cache_set` filled, first token chosen, decode cursors set), all
         ENQUEUED on the current stream without a host sync; returns a handle for `decode_finish`. Two requests can be in flight on
         two streams when they use different cache sets (prefill of one beside the decode loop of the other: SpiderFreeInfer's
@@ -480,7 +567,11 @@ class LlamaEngine:
         max(position_ids) + 1 on all three components, as transformers' rope_deltas bookkeeping does.
         eos_token_id / pad_token_id / max_new_tokens default to the checkpoint's generation config (HF behaviour):
         a row is finished at its first EOS and padded with pad_token_id afterwards; the call returns when every row is
-        finished. More than DECODE_ROWS (8) rows are processed in groups of 8 (rows are independent)."""
+        finished. More than DECODE_ROWS (8) rows are processed in groups of 8 (rows are independent).
+        repetition_penalty / min_length / min_new_tokens / suppress_tokens / bad_words_ids (single-token entries): transformers'
+        logits processors of the same names (`resolve_logits_processors`), applied on the device before the arg-max. Keyword
+        arguments only -- they are not read from the checkpoint's generation config. Neutral values (1.0, no EOS ban, empty ban
+        set) run the unprocessed kernels and decode graph."""
         if num_beams != 1 or do_sample:
             raise NotImplementedError("the reference path is greedy: num_beams=1, do_sample=False (spider.py:1471-1477)")
         c, dv = self.cfg, self.device
@@ -498,7 +589,9 @@ class LlamaEngine:
             return self._generate_grouped(input_ids, inputs_embeds, attention_mask, position_ids, B_all, dict(
                 max_new_tokens=max_new_tokens, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
                 pad_token_id=pad_token_id, output_hidden_states=output_hidden_states, use_graph=use_graph,
-                sync_every=sync_every, return_logits=return_logits, cache_set=cache_set), return_dict_in_generate)
+                sync_every=sync_every, return_logits=return_logits, cache_set=cache_set, repetition_penalty=repetition_penalty,
+                min_length=min_length, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
+                bad_words_ids=bad_words_ids), return_dict_in_generate)
         if embeds_only:
             h0 = inputs_embeds.to(device=dv, dtype=BF16).contiguous()
             B, S = h0.shape[0], h0.shape[1]
@@ -509,6 +602,10 @@ class LlamaEngine:
         if B > self.max_batch or S + max_new_tokens > self.max_len:
             raise ValueError(f"batch {B} / length {S}+{max_new_tokens} exceed the preallocated KV cache "
                              f"({self.max_batch} x {self.max_len})")
+        eos_l = _id_list(eos_token_id)
+        pen, min_new, ban = resolve_logits_processors(S, eos_l, repetition_penalty, min_length, min_new_tokens, suppress_tokens,
+                                                      bad_words_ids)
+        processed = pen != 1.0 or min_new > 0 or bool(ban)
         am = (attention_mask.to(dv).to(torch.int32) if attention_mask is not None
               else torch.ones(B, S, dtype=torch.int32, device=dv))
         pos2d = (am.cumsum(-1) - 1).clamp(min=0).to(torch.int32).contiguous()
@@ -535,14 +632,33 @@ class LlamaEngine:
 
         # decode state (static buffers + captured hipGraph) is cached per (batch, outputs): repeated generate() calls
         # replay the same graph instead of re-capturing ~200 launches
-        skey = (B, bool(output_hidden_states), bool(return_logits), int(cache_set))
+        skey = self._state_key(B, output_hidden_states, return_logits, cache_set, processed)
         if skey not in self._graphs:
-            self._graphs[skey] = [self._make_state(B, output_hidden_states, return_logits, cache_set), None]
+            self._graphs[skey] = [self._make_state(B, output_hidden_states, return_logits, cache_set, processed), None]
         st = self._graphs[skey][0]
         st["kv_beg"].copy_(kv_beg)
         last = h.view(B, S, -1)[:, -1].contiguous()
-        ops.lm_head_argmax(self.lm_head, last, norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"], ws=st["lm_ws"],
-                           logits=st.get("logits"))
+        if processed:
+            # this request's processor parameters and token sets go into the state's buffers (the captured graph reads them there);
+            # the penalised set starts as every id of the row's input_ids, pads included -- empty for an inputs_embeds call (HF)
+            st["penalty"].fill_(pen)
+            st["min_new"].fill_(min_new)
+            st["n_eos"].fill_(len(eos_l) if (eos_l and min_new > 0) else 0)
+            if eos_l and min_new > 0:
+                st["eos_ids"].copy_(torch.tensor(eos_l + [-1] * (MAX_EOS_IDS - len(eos_l)), dtype=torch.int32))
+            st["seen"].zero_()
+            st["ban"].zero_()
+            st["n_hist"].zero_()        # step 0: no token generated yet
+            if not embeds_only:
+                ops.token_bitmap_set(input_ids.to(torch.int32).contiguous(), st["seen"], c.vocab)
+            if ban:
+                ops.token_bitmap_set(torch.tensor(ban, dtype=torch.int32, device=dv)[None].expand(B, -1).contiguous(), st["ban"], c.vocab)
+            ops.lm_head_argmax_proc(self.lm_head, last, st["proc"], norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"],
+                                    ws=st["lm_ws"], logits=st.get("logits"))
+            ops.token_bitmap_set(st["next_ids"].view(B, 1), st["seen"], c.vocab)
+        else:
+            ops.lm_head_argmax(self.lm_head, last, norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"], ws=st["lm_ws"],
+                               logits=st.get("logits"))
         if output_hidden_states:
             step0[-1] = ops.rmsnorm(h, self.norm, c.eps).view(B, S, -1)
             hidden_steps.append(tuple(step0))
@@ -576,14 +692,15 @@ class LlamaEngine:
         if src == cache_set:
             return hd
         B, S = hd.B, hd.S
-        skey = hd.skey[:3] + (int(cache_set),)
+        processed = len(hd.skey) > 4
+        skey = self._state_key(B, hd.output_hidden_states, hd.return_logits, cache_set, processed)
         if skey not in self._graphs:
-            self._graphs[skey] = [self._make_state(B, hd.output_hidden_states, hd.return_logits, cache_set), None]
+            self._graphs[skey] = [self._make_state(B, hd.output_hidden_states, hd.return_logits, cache_set, processed), None]
         dst, st = self._graphs[skey][0], hd.st
         (ks, vs), (kd, vd) = self._kv(src), self._kv(cache_set)
         kd[:, :B, :, :S + 1].copy_(ks[:, :B, :, :S + 1])
         vd[:, :B, :, :S + 1].copy_(vs[:, :B, :, :S + 1])
-        for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "kv_beg", "n_hist"):
+        for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "kv_beg", "n_hist") + (self._PROC_BUFS if processed else ()):
             dst[k].copy_(st[k])
         dst["hist"][:, :1].copy_(st["hist"][:, :1])
         for k in ("logits", "hidden_buf"):
@@ -619,7 +736,7 @@ class LlamaEngine:
         final = check(1, 0)
         if use_graph and graph is None and final is None and max_new_tokens > 2:
             # warm the kernels outside capture, then capture one decode step; cursors live on device
-            snap = {k: st[k].clone() for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "n_hist")}
+            snap = {k: st[k].clone() for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "n_hist", "seen") if k in st}
             s = torch.cuda.Stream(device=dv)
             s.wait_stream(torch.cuda.current_stream(dv))
             with torch.cuda.stream(s):

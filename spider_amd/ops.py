@@ -356,6 +356,89 @@ def lm_head_argmax(W, x, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=Non
     return out_ids
 
 
+def bitmap_words(V: int) -> int:
+    return (V + 31) // 32
+
+
+def _proc_args(proc: dict, B: int, V: int):
+    """The logits-processor buffers of the *_proc lm_head forms: seen / ban int32 [B, ceil(V/32)] (uint32 bit patterns), penalty
+    float32 [1], min_new / n_eos int32 [1], eos_ids int32 [8], n_hist int32 [B]."""
+    W = bitmap_words(V)
+    for k in ("seen", "ban"):
+        _chk(proc[k], torch.int32, k)
+        assert proc[k].numel() == B * W, f"{k}: expected [{B}, {W}] words"
+    _chk(proc["penalty"], torch.float32, "penalty")
+    for k, n in (("min_new", 1), ("n_eos", 1), ("eos_ids", 8), ("n_hist", B)):
+        _chk(proc[k], torch.int32, k)
+        assert proc[k].numel() >= n, f"{k}: expected at least {n} entries"
+    return tuple(_p(proc[k]) for k in ("seen", "ban", "penalty", "min_new", "eos_ids", "n_eos", "n_hist"))
+
+
+def lm_head_argmax_proc(W, x, proc: dict, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=None):
+    """lm_head_argmax with HF's logits processors in the arg-max epilogue (repetition penalty on the ids of proc['seen'], -inf on
+    the ids of proc['ban'] and on the EOS ids while n_hist < min_new); `logits` stay the raw logits. 1 <= B <= 8."""
+    _chk(W, BF16, "W"); _chk(x, BF16, "x")
+    V, K = W.shape
+    B = x.numel() // K
+    npart = lm_head_nparts(V)
+    if ws is None:
+        ws = (torch.empty(B * npart, dtype=torch.float32, device=x.device),
+              torch.empty(B * npart, dtype=torch.int32, device=x.device))
+    assert ws[0].numel() >= B * npart and ws[1].numel() >= B * npart
+    if logits is not None:
+        assert logits.numel() == B * V
+    if out_ids is None:
+        out_ids = torch.empty(B, dtype=torch.int32, device=x.device)
+    _lib.call("spider_lm_head_argmax_proc_bf16", _p(W), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
+              _p(ws[0]), _p(ws[1]), *_proc_args(proc, B, V), B, V, K, _stream())
+    return out_ids
+
+
+def lm_head_argmax_fm_proc(Wfm, x, V, proc: dict, out_ids=None, logits=None, ws=None, norm_eps=None):
+    """lm_head_argmax_fm with the logits processors of lm_head_argmax_proc; 1 <= B <= 16."""
+    _chk(Wfm, BF16, "Wfm"); _chk(x, BF16, "x")
+    K = Wfm.shape[1] * 64
+    B = x.numel() // K
+    assert x.shape[-1] == K and Wfm.shape[0] == (V + 15) // 16
+    npart = lm_head_nparts(V)
+    if ws is None:
+        ws = (torch.empty(B * npart, dtype=torch.float32, device=x.device), torch.empty(B * npart, dtype=torch.int32, device=x.device))
+    assert ws[0].numel() >= B * npart and ws[1].numel() >= B * npart
+    if logits is not None:
+        assert logits.numel() == B * V
+    if out_ids is None:
+        out_ids = torch.empty(B, dtype=torch.int32, device=x.device)
+    _lib.call("spider_lm_head_argmax_fm_proc_bf16", _p(Wfm), _p(x), _p(out_ids), _p(logits), _p(ws[0]), _p(ws[1]),
+              *_proc_args(proc, B, V), B, V, K, int(norm_eps is not None), float(norm_eps or 0.0), _stream())
+    return out_ids
+
+
+def decode_advance_seen(next_ids, cur_ids, pos, slot, kv_end, seen, V, hist=None, n_hist=None):
+    """decode_advance, and bit next_ids[b] of seen [B, ceil(V/32)] is set (the processed greedy path's token set)."""
+    for t, n in ((next_ids, "next_ids"), (cur_ids, "cur_ids"), (pos, "pos"), (slot, "slot"), (kv_end, "kv_end"), (seen, "seen")):
+        _chk(t, torch.int32, n)
+    B = next_ids.numel()
+    assert cur_ids.numel() == B and pos.numel() == B and slot.numel() == B and kv_end.numel() == B
+    assert seen.numel() == B * bitmap_words(V)
+    cap = 0
+    if hist is not None:
+        _chk(hist, torch.int32, "hist"); _chk(n_hist, torch.int32, "n_hist")
+        assert hist.dim() == 2 and hist.shape[0] == B and n_hist.numel() == B
+        cap = hist.shape[1]
+    _lib.call("spider_decode_advance_seen_i32", _p(next_ids), _p(cur_ids), _p(pos), _p(slot), _p(kv_end), _p(hist), _p(n_hist),
+              _p(seen), V, cap, B, _stream())
+
+
+def token_bitmap_set(ids, bitmap, V):
+    """bitmap [B, ceil(V/32)] |= the bits of ids [B, n] (int32); ids outside [0, V) are ignored."""
+    _chk(ids, torch.int32, "ids"); _chk(bitmap, torch.int32, "bitmap")
+    B = bitmap.shape[0]
+    assert bitmap.dim() == 2 and bitmap.shape[1] == bitmap_words(V) and ids.numel() % B == 0
+    n = ids.numel() // B
+    if n:
+        _lib.call("spider_token_bitmap_set_i32", _p(ids), _p(bitmap), B, n, V, _stream())
+
+
 def rope_kv_append(qkv, pos, slot, cos_sin, q_out, k_cache, v_cache, B, S, n_q, n_kv, d, mrope_section=None):
     """pos [B*S] int32, or [3, B*S] with mrope_section=(t, h, w) rotary pairs per component (Qwen2.5-Omni: 16, 24, 24)."""
     _chk(qkv, BF16, "qkv"); _chk(pos, torch.int32, "pos"); _chk(slot, torch.int32, "slot")

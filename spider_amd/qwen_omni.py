@@ -676,7 +676,7 @@ class QwenOmniThinker:
 
     def would_capture(self, input_ids, attention_mask=None, cache_set: int = 0, pixel_values=None, image_grid_thw=None,
                       pixel_values_videos=None, video_grid_thw=None, input_features=None, feature_attention_mask=None,
-                      audio_feature_lengths=None, output_hidden_states: bool = False, return_logits: bool = False, decode: bool = True, **_):
+                      audio_feature_lengths=None, output_hidden_states: bool = False, return_logits: bool = False, decode: bool = True, **kw):
         """Would `generate(**inputs)` capture a hipGraph -- a tower graph for these grid_thw VALUES / audio lengths, or the decode step
         for this row count and KV cache set? Answered from the engines' own caches, so evictions and resets count. A pass that
         captures must not run beside another host thread that enqueues or allocates (SpiderFreeInfer runs it alone)."""
@@ -692,7 +692,15 @@ class QwenOmniThinker:
             return True
         if not decode:     # the prompt pass alone (SpiderFreeInfer depth 3): only the towers capture
             return False
-        return self.llm.would_capture(B, output_hidden_states, return_logits, cache_set)
+        # logits-processor keywords select the processed decode graph (LlamaEngine.prefill_begin); min_length alone does so only when
+        # it exceeds the spliced prompt length, which is not known here: then either graph missing counts
+        wc = lambda processed: self.llm.would_capture(B, output_hidden_states, return_logits, cache_set, processed=processed)
+        if kw.get("repetition_penalty") not in (None, 1, 1.0) or kw.get("suppress_tokens") or kw.get("bad_words_ids") \
+                or kw.get("min_new_tokens"):
+            return wc(True)
+        if kw.get("min_length"):
+            return wc(True) or wc(False)
+        return wc(False)
 
     @torch.no_grad()
     def adopt(self, handle, cache_set: int = 0):

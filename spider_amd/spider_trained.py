@@ -200,5 +200,6 @@ class TrainedSpider:
         outputs = self.llama_model.generate(inputs_embeds=inputs_embeds, attention_mask=attention_mask,
                                             max_new_tokens=self.max_context_len, num_beams=num_beams, do_sample=do_sample,
                                             use_cache=True, stopping_criteria=stopping, output_hidden_states=True,
-                                            return_dict_in_generate=True, output_attentions=True)
+                                            return_dict_in_generate=True, output_attentions=True,
+                                            repetition_penalty=repetition_penalty, min_length=min_length)
         return self.decode_outputs(samples, outputs, answers, predictions, predictions_text)
