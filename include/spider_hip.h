@@ -81,6 +81,26 @@ int spider_decode_advance_seen_i32(const int* next_ids, int* cur_ids, int* pos, 
 /* bitmap [B, ceil(V/32)] |= the bits of ids [B, n] (int32); ids outside [0, V) are ignored, duplicates are harmless */
 int spider_token_bitmap_set_i32(const int* ids, void* bitmap, int B, int n, int V, void* stream);
 
+/* Beam search step (transformers GenerationMixin._beam_search: _get_top_k_continuations, _get_running_beams_for_next_iteration and
+ * the cache reorder; num_beams / length_penalty reach it from spider.py:1471-1508 and conversation.py:151-173). rows = B * K.
+ * spider_beam_partial_bf16: per row of raw bf16 logits [rows, V] and slice of 4096 tokens (nslice = ceil(V / 4096)): ws_ms
+ *   [rows, nslice, 2] = (max, sum exp(x - max)) in fp32, ws_val / ws_tok [rows, nslice, C] = the slice's C best logits and tokens
+ *   (value descending, token ascending; token -1 where the slice has fewer than C tokens). 1 <= C <= 32.
+ * spider_beam_select_f32: per batch row, score = run_scores[b, k] + (logit - lse[k]) in fp32; the C best continuations ordered by
+ *   score descending, then k * V + token ascending, go to trace_score / trace_beam / trace_tok [cap, B, C] at step n_hist[b * K]
+ *   (dropped when >= cap); the first K of them whose token is none of the n_eos[0] (<= 8) ids of eos_ids become the running beams:
+ *   run_scores [B, K] (in place), src_beam [B, K] (beam index within the batch row), next_ids [B * K]. K <= 8, K <= C <= V.
+ * spider_kv_row_gather_bf16: caches [layers, rows_alloc, n_kv, T, d]: row r <- old row (r / K) * K + src_beam[r] over the slots
+ *   [kv_beg[r], kv_end[r]), for r < R, any map (two launches through k_tmp / v_tmp of the same layout; rows mapped to themselves
+ *   are not touched). K = R makes src_beam an absolute row map. d % 8 == 0. */
+int spider_beam_partial_bf16(const void* logits, float* ws_ms, float* ws_val, int* ws_tok, int rows, int V, int C, int nslice,
+                             void* stream);
+int spider_beam_select_f32(const float* ws_ms, const float* ws_val, const int* ws_tok, float* run_scores, const int* eos_ids,
+                           const int* n_eos, const int* n_hist, float* trace_score, int* trace_beam, int* trace_tok, int cap,
+                           int* src_beam, int* next_ids, int B, int K, int V, int C, int nslice, void* stream);
+int spider_kv_row_gather_bf16(void* k_cache, void* v_cache, void* k_tmp, void* v_tmp, const int* src_beam, const int* kv_beg,
+                              const int* kv_end, int K, int R, int layers, int rows_alloc, int n_kv, int T, int d, void* stream);
+
 /* apply_rotary_pos_emb (modeling_llama3.py:150-183; modeling_llama.py:116-123) on q,k of a fused QKV
  * projection + KV-cache append (modeling_llama.py:190-193). qkv [B*S,(n_q+2n_kv)*d]; cos_sin fp32
  * [max_pos, d] = [cos(d/2) | sin(d/2)]; q_out [B*S,n_q,d]; caches [B,n_kv,T_max,d]. */

@@ -20,6 +20,11 @@ Decode = 5 weight-streaming launches per layer (+1 tiny split-KV combine), captu
 Logits processors (opt-in keywords of generate: repetition_penalty, min_length / min_new_tokens, suppress_tokens, single-token
 bad_words_ids -- what spider.py:1471-1508 and conversation.py:151-172 forward to HF's generate) run in the arg-max epilogue of the
 lm_head kernels on per-sequence token bitmaps kept in the decode state; neutral values use the unprocessed kernels and graph.
+
+Beam search (num_beams 2..8, with length_penalty / early_stopping / num_return_sequences): the beam step of transformers'
+`_beam_search` -- log-softmax of the raw logits, the best continuations of a batch row's K beams, the KV-cache reorder -- is three
+launches behind the lm_head inside the captured decode graph (csrc/beam_search.hip); `beam_finalize_host` replays HF's
+finished-hypotheses bookkeeping on the trace the device wrote. num_beams=1 is the greedy path, unchanged.
 """
 from __future__ import annotations
 
@@ -219,6 +224,140 @@ def finalize_greedy(tokens: torch.Tensor, eos: Optional[List[int]], pad: Optiona
     return tk, n, False
 
 
+BEAM_MAX_K = 8          # beams per batch row (the decode graph holds DECODE_ROWS = 8 rows)
+BEAM_MAX_C = 32         # continuations kept per batch row and step by the selection kernel
+
+
+def resolve_beam_search(B: int, num_beams, max_batch: int, vocab: int, eos: Optional[List[int]], decode_rows: int = 8,
+                        do_sample: bool = False, stopping_criteria=None, output_hidden_states: bool = False, processed: bool = False,
+                        num_beam_groups=1, constraints=None, force_words_ids=None, num_return_sequences=1, length_penalty=1.0,
+                        early_stopping=False) -> int:
+    """Validate a `generate(num_beams > 1, ...)` request against what the beam path implements and return C, the number of
+    continuations kept per batch row and step: transformers' `beams_to_keep = max(2, 1 + n_eos) * num_beams` (sized so that
+    num_beams unfinished ones always exist). Everything outside the implemented ground raises; nothing is ignored."""
+    if not isinstance(num_beams, int) or isinstance(num_beams, bool) or not (2 <= num_beams <= BEAM_MAX_K):
+        raise ValueError(f"num_beams has to be an integer in [1, {BEAM_MAX_K}], but is {num_beams}")
+    if do_sample:
+        raise NotImplementedError("beam-search multinomial sampling (num_beams > 1 with do_sample=True) is not implemented")
+    if num_beam_groups not in (None, 1):
+        raise NotImplementedError("group beam search (num_beam_groups > 1) is not implemented")
+    if constraints or force_words_ids:
+        raise NotImplementedError("constrained beam search (constraints / force_words_ids) is not implemented")
+    if stopping_criteria:
+        raise NotImplementedError("user stopping_criteria with num_beams > 1 are not implemented (EOS ids and max_new_tokens end a beam)")
+    if output_hidden_states:
+        raise NotImplementedError("output_hidden_states with num_beams > 1 is not implemented")
+    if processed:
+        raise NotImplementedError("repetition_penalty / min_length / min_new_tokens / suppress_tokens / bad_words_ids with "
+                                  "num_beams > 1 are not implemented: pass their neutral values")
+    if B * num_beams > decode_rows or B * num_beams > max_batch:
+        raise ValueError(f"batch {B} x num_beams {num_beams} = {B * num_beams} rows exceed the decode graph's {decode_rows} rows "
+                         f"or the engine's max_batch={max_batch}")
+    if not isinstance(num_return_sequences, int) or not (1 <= num_return_sequences <= num_beams):
+        raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be in [1, num_beams={num_beams}]")
+    if not (early_stopping is True or early_stopping is False or early_stopping == "never"):
+        raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {early_stopping}")
+    if not isinstance(length_penalty, (int, float)) or isinstance(length_penalty, bool):
+        raise ValueError(f"`length_penalty` has to be a number, but is {length_penalty}")
+    n_eos = len(eos) if eos else 0
+    if n_eos > MAX_EOS_IDS:
+        raise ValueError(f"at most {MAX_EOS_IDS} eos_token_id values are supported with num_beams > 1")
+    C = max(2, 1 + n_eos) * num_beams
+    if C > BEAM_MAX_C or C > vocab:
+        raise ValueError(f"max(2, 1 + n_eos) * num_beams = {C} continuations per step exceed the selection kernel's {BEAM_MAX_C} "
+                         f"(or the vocabulary, {vocab})")
+    return C
+
+
+class _BeamHostState:
+    """The finished-hypotheses state of transformers' `_beam_search`, in generated-token coordinates (prompt length 0)."""
+
+    def __init__(self, B, K, max_new, fill):
+        self.B, self.K, self.t, self.done = B, K, 0, False
+        self.running_seq = torch.full((B, K, max_new), fill, dtype=torch.int64)
+        self.seq = self.running_seq.clone()
+        self.running_idx = torch.full((B, K, max_new), -1, dtype=torch.int32)
+        self.idx = self.running_idx.clone()
+        self.running_scores = torch.zeros(B, K, dtype=torch.float32)
+        self.running_scores[:, 1:] = -1e9
+        self.scores = torch.full((B, K), -1e9, dtype=torch.float32)
+        self.finished = torch.zeros(B, K, dtype=torch.bool)
+        self.unsat = torch.ones(B, 1, dtype=torch.bool)      # is_early_stop_heuristic_unsatisfied
+
+
+def beam_finalize_host(trace, num_beams: int, max_new_tokens: int, eos: Optional[List[int]], pad: Optional[int],
+                       length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
+                       prompt: Optional[torch.Tensor] = None, state: Optional[_BeamHostState] = None, first_step: int = 0):
+    """HF beam-search bookkeeping (transformers 5.x `GenerationMixin._beam_search` with `_update_finished_beams`,
+    `_check_early_stop_heuristic`, `_beam_search_has_unfinished_sequences`; num_beams / length_penalty arrive from spider.py:1471-1508
+    and conversation.py:151-173), replayed on the CPU over the trace the device wrote: trace = (score f32, beam, token), each
+    [n, B, C], the C best continuations of steps first_step .. first_step + n - 1 in score order (beam = source beam within the batch
+    row). The running beams of the next step are the first K continuations that neither are an EOS id nor reach max_new_tokens --
+    what the device chose without asking. Same fp32 torch expressions as HF, so scores are equal, not close.
+    Returns (result, state): result is None while HF's loop would still run (call again with the later steps and `state`); else a
+    dict: sequences [B * num_return_sequences, S + n] (prompt [B, S] prepended when given; short ones filled as HF fills them:
+    pad_token_id, or eos[0] when that is None or 0), sequences_scores, beam_indices (row b * K + beam per generated token, -1 past
+    the end) and n_steps, the number of steps HF's loop ran (later steps of the trace are over-decode and ignored)."""
+    score, beam, tok = (t.cpu() for t in trace)
+    n, B, C = score.shape
+    K = int(num_beams)
+    eos_t = torch.tensor(eos) if eos else None
+    if state is None:
+        fill = (pad if pad else eos[0]) if eos else -1        # HF: `pad_token_id or eos_token_id[0] if eos_token_id is not None else -1`
+        state = _BeamHostState(B, K, max_new_tokens, fill)
+    st = state
+    assert first_step <= st.t, "beam_finalize_host: the trace block starts after the first step not yet replayed"
+    top_mask = torch.cat([torch.ones(K, dtype=torch.bool), torch.zeros(C - K, dtype=torch.bool)])
+    take = lambda x, i: torch.take_along_dim(x, i.reshape(i.shape + (1,) * (x.dim() - i.dim())), dim=1)
+    while not st.done and st.t - first_step < n:
+        t = st.t
+        lp, bi, tk = score[t - first_step].float(), beam[t - first_step].long(), tok[t - first_step].long()
+        # _get_top_k_continuations: the candidates' sequences and back-pointers
+        topk_seq = take(st.running_seq, bi)
+        topk_idx = take(st.running_idx, bi)
+        topk_seq[:, :, t] = tk
+        topk_idx[:, :, t] = (bi + torch.arange(B)[:, None] * K).to(torch.int32)
+        # stopping criteria of a candidate: EosTokenCriteria | MaxLengthCriteria
+        hits = torch.isin(tk, eos_t) if eos_t is not None else torch.zeros_like(tk, dtype=torch.bool)
+        if t + 1 >= max_new_tokens:
+            hits = torch.ones_like(hits)
+        # _get_running_beams_for_next_iteration
+        run_lp = lp + hits.to(torch.float32) * -1.0e9
+        sel = torch.argsort(hits.long() * C + torch.arange(C)[None], dim=1)[:, :K]
+        st.running_seq, st.running_scores, st.running_idx = take(topk_seq, sel), take(run_lp, sel), take(topk_idx, sel)
+        # _update_finished_beams
+        did = hits & top_mask[None, :]
+        flp = lp / ((t + 1) ** length_penalty)
+        full = torch.all(st.finished, dim=-1, keepdim=True) & (early_stopping is True)
+        flp = flp + full.to(torch.float32) * -1.0e9
+        flp = flp + (~st.unsat).to(torch.float32) * -1.0e9
+        flp = flp + (~did) * -1.0e9
+        m_scores = torch.cat((st.scores, flp), dim=1)
+        pick = torch.topk(m_scores, k=K)[1]
+        st.seq = take(torch.cat((st.seq, topk_seq), dim=1), pick)
+        st.scores = take(m_scores, pick)
+        st.idx = take(torch.cat((st.idx, topk_idx), dim=1), pick)
+        st.finished = take(torch.cat((st.finished, did), dim=1), pick)
+        st.t = t + 1
+        # _check_early_stop_heuristic at the new length, _beam_search_has_unfinished_sequences
+        best_len = max_new_tokens if (early_stopping == "never" and length_penalty > 0.0) else st.t
+        best_running = st.running_scores[:, :1] / (best_len ** length_penalty)
+        worst_fin = torch.where(st.finished, torch.min(st.scores, dim=1, keepdim=True)[0], -1.0e9)
+        st.unsat = st.unsat & torch.any(best_running > worst_fin, dim=-1, keepdim=True)
+        go_on = torch.any(st.unsat) & ~(torch.all(st.finished) & (early_stopping is True)) & ~torch.all(hits)
+        st.done = not bool(go_on)
+    if not st.done:
+        return None, st
+    R = int(num_return_sequences)
+    seqs = st.seq[:, :R].reshape(B * R, -1)
+    idx = st.idx[:, :R].reshape(B * R, -1)
+    n_gen = int(((idx + 1).bool()).sum(dim=1).max())
+    seqs = seqs[:, :n_gen]
+    if prompt is not None:
+        seqs = torch.cat([prompt.cpu().long().repeat_interleave(R, dim=0), seqs], 1)
+    return dict(sequences=seqs, sequences_scores=st.scores[:, :R].reshape(B * R), beam_indices=idx[:, :n_gen], n_steps=st.t), st
+
+
 _FUSE_SWIGLU = os.environ.get("SPIDER_PREFILL_SWIGLU_FUSE", "1") != "0"     # tuning aid: 0 = separate SwiGLU launch after the gate/up GEMM
 
 
@@ -230,9 +369,11 @@ class _PrefillHandle:
 
 
 class GenerateOutput:
-    def __init__(self, sequences, hidden_states=None):
+    def __init__(self, sequences, hidden_states=None, sequences_scores=None, beam_indices=None):
         self.sequences = sequences
         self.hidden_states = hidden_states
+        self.sequences_scores = sequences_scores     # beam search only (num_beams > 1)
+        self.beam_indices = beam_indices
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -346,6 +487,7 @@ class LlamaEngine:
         self._kv_sets = [(self.k_cache, self.v_cache)]
         self.cos_sin = rope_table(c, max(c.max_pos, T)).to(dv)
         self._graphs = {}
+        self._beam_kv_tmp = {}      # cache set -> second K / V buffer of the beam-search reorder (allocated by the first beam request)
 
     def _kv(self, cache_set: int):
         while len(self._kv_sets) <= cache_set:
@@ -401,16 +543,22 @@ class LlamaEngine:
         self._vocab_changed()
 
     @staticmethod
-    def _state_key(B: int, output_hidden_states: bool, return_logits: bool, cache_set: int, processed: bool = False) -> tuple:
-        """key of a decode state + captured graph; requests with logits processors have their own (one more element)"""
+    def _state_key(B: int, output_hidden_states: bool, return_logits: bool, cache_set: int, processed: bool = False,
+                   beam: Optional[tuple] = None) -> tuple:
+        """key of a decode state + captured graph; requests with logits processors have their own (one more element), and so have
+        beam-search requests (B = batch rows; beam = (num_beams, continuations kept per step): three more elements)"""
         key = (int(B), bool(output_hidden_states), bool(return_logits), int(cache_set))
+        if beam is not None:
+            return key + ("beam", int(beam[0]), int(beam[1]))
         return key + (True,) if processed else key
 
     def would_capture(self, B: int, output_hidden_states: bool = False, return_logits: bool = False, cache_set: int = 0,
-                      processed: bool = False) -> bool:
+                      processed: bool = False, num_beams: int = 1, n_eos: int = 0) -> bool:
         """True when the decode loop of such a request would capture its hipGraph (state missing or not captured yet).
-        processed: a request with non-neutral logits processors (repetition_penalty != 1, a ban set, or EOS banned at first)"""
-        ent = self._graphs.get(self._state_key(B, output_hidden_states, return_logits, cache_set, processed))
+        processed: a request with non-neutral logits processors (repetition_penalty != 1, a ban set, or EOS banned at first)
+        num_beams > 1: a beam-search request of B batch rows with n_eos EOS ids (they size the continuations kept per step)"""
+        beam = (num_beams, max(2, 1 + n_eos) * num_beams) if num_beams > 1 else None
+        ent = self._graphs.get(self._state_key(B, output_hidden_states, return_logits, cache_set, processed, beam))
         return ent is None or ent[1] is None
 
     def _vocab_changed(self):
@@ -419,6 +567,7 @@ class LlamaEngine:
         if self.fm_batch:
             self.lm_head_fm = ops.repack_fm16(self.lm_head, self.norm)
         self._graphs = {}
+        self._beam_kv_tmp = {}      # held by the beam states just dropped
 
     # ------------------------------------------------------------------ prefill
     def _prefill(self, h: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, kv_beg: Optional[torch.Tensor],
@@ -485,6 +634,16 @@ class LlamaEngine:
                 h = ops.gemv(lw["w_down"], st["act"], res=h1, out=st["h2"][l & 1])
             if hs is not None:
                 hs[l + 1].copy_(h)
+        if st.get("beam") is not None:      # beam search: the raw logits of the B * K rows go to the beam step instead of an arg-max
+            bm = st["beam"]
+            if fm:
+                ops.lm_head_argmax_fm(self.lm_head_fm, h, c.vocab, out_ids=bm["lm_ids"], ws=st["lm_ws"], logits=st["logits"],
+                                      norm_eps=c.eps)
+            else:
+                ops.lm_head_argmax(self.lm_head, h, norm_w=self.norm, eps=c.eps, out_ids=bm["lm_ids"], ws=st["lm_ws"],
+                                   logits=st["logits"])
+            self._beam_step(st)
+            return
         proc = st.get("proc")      # logits processors in the arg-max epilogue (their parameters are read from the state's buffers)
         if proc is not None and fm:
             ops.lm_head_argmax_fm_proc(self.lm_head_fm, h, c.vocab, proc, out_ids=st["next_ids"], ws=st["lm_ws"],
@@ -507,9 +666,23 @@ class LlamaEngine:
         else:
             ops.decode_advance(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["hist"], st["n_hist"])
 
+    def _beam_step(self, st: dict, reorder: bool = True):
+        """Behind the lm_head of a beam-search step (graph-capturable, no host sync): the C best continuations of every batch row go
+        to the trace, the first K non-EOS ones become the running beams (scores, tokens), the KV rows follow their source beams and
+        the cursors advance. reorder=False: selection only (step 0, whose rows are still the un-expanded prompt rows)."""
+        bm, c = st["beam"], self.cfg
+        ops.beam_partial(st["logits"], bm["C"], bm["ws"])
+        ops.beam_select(bm["ws"], bm["run"], bm["eos_ids"], bm["n_eos"], st["n_hist"], bm["trace"], bm["src_beam"], st["next_ids"],
+                        c.vocab, bm["C"])
+        if reorder:
+            ops.kv_row_gather(st["kv"][0], st["kv"][1], bm["kv_tmp"][0], bm["kv_tmp"][1], bm["src_beam"], st["kv_beg"], st["kv_end"],
+                              bm["K"])
+            ops.decode_advance(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["hist"], st["n_hist"])
+
     _PROC_BUFS = ("seen", "ban", "penalty", "min_new", "eos_ids", "n_eos")
 
-    def _make_state(self, B: int, want_hidden: bool, want_logits: bool, cache_set: int = 0, processed: bool = False) -> dict:
+    def _make_state(self, B: int, want_hidden: bool, want_logits: bool, cache_set: int = 0, processed: bool = False,
+                    beam: Optional[tuple] = None) -> dict:
         c, dv = self.cfg, self.device
         nq_d = c.n_q * c.head_dim
         # one split-KV block per CU (256): measured on Qwen-7B shapes at T~1.6k: 2.93 / 2.90 / 3.14 ms per token at 32 / 64 / 96 splits
@@ -535,13 +708,23 @@ class LlamaEngine:
             st.update(seen=i32(B, W), ban=i32(B, W), penalty=torch.ones(1, dtype=torch.float32, device=dv), min_new=i32(1),
                       eos_ids=i32(MAX_EOS_IDS), n_eos=i32(1))
             st["proc"] = {k: st[k] for k in self._PROC_BUFS + ("n_hist",)}
+        if beam is not None:    # B = batch rows * K here. The trace holds max_len steps; the second KV buffer belongs to the cache set
+            K, C = beam
+            nb = B // K
+            if cache_set not in self._beam_kv_tmp:
+                self._beam_kv_tmp[cache_set] = (torch.zeros_like(self.k_cache), torch.zeros_like(self.v_cache))
+            st["beam"] = dict(K=K, C=C, run=torch.zeros(nb, K, dtype=torch.float32, device=dv), src_beam=i32(nb, K), lm_ids=i32(B),
+                              eos_ids=i32(MAX_EOS_IDS), n_eos=i32(1), ws=ops.beam_workspace(B, c.vocab, C, dv),
+                              trace=(torch.zeros(self.max_len, nb, C, dtype=torch.float32, device=dv), i32(self.max_len, nb, C),
+                                     i32(self.max_len, nb, C)),
+                              kv_tmp=self._beam_kv_tmp[cache_set])
         return st
 
     # ------------------------------------------------------------------ public generate
     @torch.no_grad()
     def generate(self, input_ids: Optional[torch.Tensor] = None, inputs_embeds: Optional[torch.Tensor] = None, **kw):
         """Greedy decode = `prefill_begin` + `decode_finish` back to back (arguments: see prefill_begin)."""
-        h = self.prefill_begin(input_ids, inputs_embeds, **kw)
+        h = self.prefill_begin(input_ids, inputs_embeds, _whole_generate=True, **kw)
         return self.decode_finish(h) if isinstance(h, _PrefillHandle) else h
 
     @torch.no_grad()
@@ -552,7 +735,9 @@ class LlamaEngine:
                       num_beams: int = 1, do_sample: bool = False, use_cache: bool = True, output_attentions: bool = False,
                       use_graph: bool = True, sync_every: int = 1, return_logits: bool = False,
                       position_ids: Optional[torch.Tensor] = None, cache_set: int = 0, repetition_penalty=1.0, min_length=0,
-                      min_new_tokens=0, suppress_tokens=None, bad_words_ids=None, **unused):
+                      min_new_tokens=0, suppress_tokens=None, bad_words_ids=None, length_penalty=1.0, early_stopping=False,
+                      num_return_sequences=1, num_beam_groups=1, constraints=None, force_words_ids=None, _whole_generate=False,
+                      **unused):
         """First half of `generate`: the prompt pass (KV cache of `cache_set` filled, first token chosen, decode cursors set), all
         ENQUEUED on the current stream without a host sync; returns a handle for `decode_finish`. Two requests can be in flight on
         two streams when they use different cache sets (prefill of one beside the decode loop of the other: SpiderFreeInfer's
@@ -571,8 +756,15 @@ class LlamaEngine:
         repetition_penalty / min_length / min_new_tokens / suppress_tokens / bad_words_ids (single-token entries): transformers'
         logits processors of the same names (`resolve_logits_processors`), applied on the device before the arg-max. Keyword
         arguments only -- they are not read from the checkpoint's generation config. Neutral values (1.0, no EOS ban, empty ban
-        set) run the unprocessed kernels and decode graph."""
-        if num_beams != 1 or do_sample:
+        set) run the unprocessed kernels and decode graph.
+        num_beams > 1 (2..8, batch * num_beams <= DECODE_ROWS and <= max_batch): transformers' beam search with length_penalty,
+        early_stopping (False / True / "never") and num_return_sequences. The beam step runs on the device inside the decode graph
+        and `beam_finalize_host` replays HF's finished-hypotheses bookkeeping at the `sync_every` points. Only `generate` accepts it
+        (its decode loop syncs with the host, so there is no handle to return): a direct prefill_begin(num_beams > 1) raises.
+        `generate` returns sequences [B * num_return_sequences, ...], with return_dict_in_generate also
+        sequences_scores and beam_indices, with return_logits the running beams' raw logits [B * num_beams, n, V]. Sampling, user
+        stopping_criteria, output_hidden_states, non-neutral logits processors, beam groups and constraints raise."""
+        if do_sample and num_beams == 1:
             raise NotImplementedError("the reference path is greedy: num_beams=1, do_sample=False (spider.py:1471-1477)")
         c, dv = self.cfg, self.device
         gc = getattr(self, "generation_config", None) or {}
@@ -585,6 +777,18 @@ class LlamaEngine:
         if max_new_tokens is None:   # HF: generation_config.max_new_tokens, else max_length (default 20) counts the prompt
             max_new_tokens = gc.get("max_new_tokens") or max(1, int(gc.get("max_length", 20)) - (0 if embeds_only else S_in))
         B_all = inputs_embeds.shape[0] if embeds_only else input_ids.shape[0]
+        beam = None
+        if num_beams != 1 and not _whole_generate:
+            raise NotImplementedError("num_beams > 1 runs through LlamaEngine.generate only: the split prefill_begin / adopt / decode_finish "
+                                      "path (SpiderFreeInfer's pipelining, QwenOmniThinker) is greedy")
+        if num_beams != 1:
+            pen, min_new, ban = resolve_logits_processors(S_in, _id_list(eos_token_id), repetition_penalty, min_length, min_new_tokens,
+                                                          suppress_tokens, bad_words_ids)
+            C_keep = resolve_beam_search(B_all, num_beams, self.max_batch, c.vocab, _id_list(eos_token_id), self.DECODE_ROWS, do_sample,
+                                         stopping_criteria, output_hidden_states, pen != 1.0 or min_new > 0 or bool(ban),
+                                         num_beam_groups, constraints, force_words_ids, num_return_sequences, length_penalty,
+                                         early_stopping)
+            beam = (num_beams, C_keep)
         if B_all > self.DECODE_ROWS:
             return self._generate_grouped(input_ids, inputs_embeds, attention_mask, position_ids, B_all, dict(
                 max_new_tokens=max_new_tokens, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
@@ -629,6 +833,10 @@ class LlamaEngine:
             h = self._prefill(h0.view(B * S, -1), pos2d.view(-1), slot2d.view(-1), kv_beg if has_pad else None, B, S, step0,
                               cache_set=cache_set)
             next_pos = pos2d[:, -1] + 1
+        if beam is not None:
+            return self._beam_decode(beam, h.view(B, S, -1)[:, -1], next_pos, kv_beg, B, S, None if embeds_only else input_ids,
+                                     max_new_tokens, eos_l, pad_token_id, float(length_penalty), early_stopping, num_return_sequences,
+                                     return_dict_in_generate, use_graph, max(1, int(sync_every)), return_logits, cache_set)
 
         # decode state (static buffers + captured hipGraph) is cached per (batch, outputs): repeated generate() calls
         # replay the same graph instead of re-capturing ~200 launches
@@ -778,6 +986,75 @@ class LlamaEngine:
         if return_logits:
             out.logits = torch.stack(logits_steps, 1)
         return out if return_dict_in_generate else seqs
+
+    def _beam_decode(self, beam, last, next_pos, kv_beg, B, S, input_ids, max_new_tokens, eos, pad, length_penalty, early_stopping,
+                     num_return_sequences, as_dict, use_graph, sync_every, return_logits, cache_set):
+        """Beam search behind the prompt pass (which ran once per batch row: `last` [B, H] is its final residual at the last
+        position). Step 0 scores K copies of that row (HF's score vector [0, -1e9, ...] keeps beam 0 only), the prompt's KV rows are
+        expanded to row b * K + k <- row b with the reorder kernel, then every decode step is one graph replay; the host reads the
+        trace every `sync_every` steps and stops at the step HF's loop ends (`beam_finalize_host`)."""
+        c, dv = self.cfg, self.device
+        K, C = beam
+        R = B * K
+        if max_new_tokens > self.max_len:
+            raise ValueError(f"max_new_tokens={max_new_tokens} exceeds the engine's max_len={self.max_len}")
+        skey = self._state_key(B, False, return_logits, cache_set, False, beam)
+        if skey not in self._graphs:
+            self._graphs[skey] = [self._make_state(R, False, True, cache_set, False, beam), None]
+        st = self._graphs[skey][0]
+        bm = st["beam"]
+        rep = lambda t: t.repeat_interleave(K, 0).contiguous()
+        bm["run"].copy_(torch.tensor([0.0] + [-1e9] * (K - 1), dtype=torch.float32)[None].expand(B, K))
+        bm["n_eos"].fill_(len(eos) if eos else 0)
+        bm["eos_ids"].copy_(torch.tensor((eos or []) + [-1] * (MAX_EOS_IDS - len(eos or [])), dtype=torch.int32))
+        st["n_hist"].zero_()
+        ops.lm_head_argmax(self.lm_head, rep(last), norm_w=self.norm, eps=c.eps, out_ids=bm["lm_ids"], ws=st["lm_ws"], logits=st["logits"])
+        self._beam_step(st, reorder=False)
+        st["kv_beg"].copy_(rep(kv_beg))
+        st["kv_end"].fill_(S)
+        row_map = rep(torch.arange(B, dtype=torch.int32, device=dv))
+        ops.kv_row_gather(st["kv"][0], st["kv"][1], bm["kv_tmp"][0], bm["kv_tmp"][1], row_map, st["kv_beg"], st["kv_end"], R)
+        st["cur_ids"].copy_(st["next_ids"])
+        st["pos"].copy_(rep(next_pos.to(torch.int32)))
+        st["slot"].fill_(S)
+        st["kv_end"].fill_(S + 1)
+        st["n_hist"].fill_(1)
+        logits_steps = [st["logits"].clone()] if return_logits else None
+        prompt_cpu = None if input_ids is None else input_ids.cpu().long()
+        host = [None, None, 0]      # (result, bookkeeping state, steps already handed to the host)
+
+        def check(n_done: int):
+            blk = tuple(t[host[2]:n_done].cpu() for t in bm["trace"])
+            host[0], host[1] = beam_finalize_host(blk, K, max_new_tokens, eos, pad, length_penalty, early_stopping,
+                                                  num_return_sequences, prompt_cpu, host[1], host[2])
+            host[2] = n_done
+
+        graph = self._graphs[skey][1] if use_graph else None
+        n = 1
+        check(1)
+        while n < max_new_tokens and host[0] is None:
+            if graph is not None:
+                graph.replay()
+            else:
+                self._decode_step(st)
+                if use_graph and max_new_tokens - n > 2:
+                    # That eager step was a real one and loaded the kernels; the following ones replay its capture. (A warm-up step
+                    # that is rolled back, as on the greedy path, would have to undo the reorder of the KV rows as well.)
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        self._decode_step(st)
+                    self._graphs[skey][1] = graph
+            if return_logits:
+                logits_steps.append(st["logits"].clone())
+            n += 1
+            if n % sync_every == 0 or n == max_new_tokens:
+                check(n)
+        res = host[0]
+        seqs = res["sequences"].to(dv)
+        out = GenerateOutput(seqs, None, res["sequences_scores"].to(dv), res["beam_indices"].to(dv))
+        if return_logits:
+            out.logits = torch.stack(logits_steps[:res["n_steps"]], 1)
+        return out if as_dict else seqs
 
     def _generate_grouped(self, input_ids, inputs_embeds, attention_mask, position_ids, B_all: int, kw: dict, as_dict: bool):
         """More rows than one decode graph holds: groups of DECODE_ROWS, results joined the way one HF call would return

@@ -439,6 +439,66 @@ def token_bitmap_set(ids, bitmap, V):
         _lib.call("spider_token_bitmap_set_i32", _p(ids), _p(bitmap), B, n, V, _stream())
 
 
+BEAM_SLICE = 4096       # tokens per block of beam_partial (beam_search.hip)
+BEAM_MAX_C = 32
+
+
+def beam_nslices(V: int) -> int:
+    return (V + BEAM_SLICE - 1) // BEAM_SLICE
+
+
+def beam_workspace(rows: int, V: int, C: int, device):
+    """(ws_ms [rows, nslice, 2] f32, ws_val [rows, nslice, C] f32, ws_tok [rows, nslice, C] i32) of beam_partial / beam_select"""
+    ns = beam_nslices(V)
+    return (torch.empty(rows, ns, 2, dtype=torch.float32, device=device), torch.empty(rows, ns, C, dtype=torch.float32, device=device),
+            torch.empty(rows, ns, C, dtype=torch.int32, device=device))
+
+
+def beam_partial(logits, C, ws):
+    """Per row of raw bf16 logits [rows, V] and slice of 4096 tokens: the online-softmax pair and the slice's C best (logit, token)."""
+    _chk(logits, BF16, "logits")
+    rows, V = logits.shape
+    ns = beam_nslices(V)
+    _chk(ws[0], torch.float32, "ws_ms"); _chk(ws[1], torch.float32, "ws_val"); _chk(ws[2], torch.int32, "ws_tok")
+    assert ws[0].numel() == rows * ns * 2 and ws[1].numel() == rows * ns * C and ws[2].numel() == rows * ns * C
+    _lib.call("spider_beam_partial_bf16", _p(logits), _p(ws[0]), _p(ws[1]), _p(ws[2]), rows, V, C, ns, _stream())
+
+
+def beam_select(ws, run_scores, eos_ids, n_eos, n_hist, trace, src_beam, next_ids, V, C):
+    """One beam-search selection per batch row from beam_partial's workspace: run_scores [B, K] f32 (updated in place), the C best
+    continuations (score descending, then beam * V + token ascending) written to trace = (score f32, beam i32, token i32), each
+    [cap, B, C], at step n_hist[b * K]; the first K non-EOS of them -> run_scores, src_beam [B, K], next_ids [B * K]."""
+    _chk(run_scores, torch.float32, "run_scores"); _chk(eos_ids, torch.int32, "eos_ids"); _chk(n_eos, torch.int32, "n_eos")
+    _chk(n_hist, torch.int32, "n_hist"); _chk(src_beam, torch.int32, "src_beam"); _chk(next_ids, torch.int32, "next_ids")
+    _chk(trace[0], torch.float32, "trace_score"); _chk(trace[1], torch.int32, "trace_beam"); _chk(trace[2], torch.int32, "trace_tok")
+    B, K = run_scores.shape
+    ns = beam_nslices(V)
+    if not (1 <= K <= 8 and K <= C <= BEAM_MAX_C and V >= C):
+        raise ValueError(f"beam_select: needs K <= 8 and K <= C <= {BEAM_MAX_C} <= V (K={K}, C={C}, V={V})")
+    assert ws[0].numel() == B * K * ns * 2 and ws[1].numel() == B * K * ns * C and ws[2].numel() == B * K * ns * C
+    assert eos_ids.numel() >= 8 and n_eos.numel() == 1 and n_hist.numel() == B * K
+    assert src_beam.numel() == B * K and next_ids.numel() == B * K
+    cap = trace[0].shape[0]
+    for t in trace:
+        assert tuple(t.shape) == (cap, B, C)
+    _lib.call("spider_beam_select_f32", _p(ws[0]), _p(ws[1]), _p(ws[2]), _p(run_scores), _p(eos_ids), _p(n_eos), _p(n_hist),
+              _p(trace[0]), _p(trace[1]), _p(trace[2]), cap, _p(src_beam), _p(next_ids), B, K, V, C, ns, _stream())
+
+
+def kv_row_gather(k_cache, v_cache, k_tmp, v_tmp, src_beam, kv_beg, kv_end, K):
+    """Caches [layers, rows_alloc, n_kv, T, d]: row r <- old row (r // K) * K + src_beam[r] over slots [kv_beg[r], kv_end[r]) for
+    the R = src_beam.numel() first rows, correct for any map (through k_tmp / v_tmp); K = R: src_beam is an absolute row map."""
+    for t, n in ((k_cache, "k_cache"), (v_cache, "v_cache"), (k_tmp, "k_tmp"), (v_tmp, "v_tmp")):
+        _chk(t, BF16, n)
+        assert t.shape == k_cache.shape and t.dim() == 5
+    _chk(src_beam, torch.int32, "src_beam"); _chk(kv_beg, torch.int32, "kv_beg"); _chk(kv_end, torch.int32, "kv_end")
+    L, RA, n_kv, T, d = k_cache.shape
+    R = src_beam.numel()
+    assert kv_beg.numel() == R and kv_end.numel() == R and R <= RA and R % K == 0
+    _lib.call("spider_kv_row_gather_bf16", _p(k_cache), _p(v_cache), _p(k_tmp), _p(v_tmp), _p(src_beam), _p(kv_beg), _p(kv_end),
+              K, R, L, RA, n_kv, T, d, _stream())
+
+
 def rope_kv_append(qkv, pos, slot, cos_sin, q_out, k_cache, v_cache, B, S, n_q, n_kv, d, mrope_section=None):
     """pos [B*S] int32, or [3, B*S] with mrope_section=(t, h, w) rotary pairs per component (Qwen2.5-Omni: 16, 24, 24)."""
     _chk(qkv, BF16, "qkv"); _chk(pos, torch.int32, "pos"); _chk(slot, torch.int32, "slot")
