@@ -134,6 +134,12 @@ int spider_attn_decode_fused_bf16(const void* qkv, const int* pos, const float* 
  * block; 1: acq_rel ticket, 2: write-through partials + relaxed ticket + sc1 loads, no fence), 0 = in the separate combine launch
  * (SPIDER_ATTN_INLINE is read once, at the first call). Returns the previous setting. */
 int spider_set_attn_inline(int on);
+/* Tuning / test aid: memory schedule of the decode GEMVs (spider_gemv_bf16 / spider_gemv_swiglu_bf16, 1..8 sequences): 0 = one request
+ * at a time (activation staging vector by vector, the next weight chunks requested after the previous ones are consumed), 1 = one round
+ * trip per block (default: activations and the hoisted weight chunks -- the whole row where K <= 4096 -- requested together, two register
+ * sets in the long-K loop). Same arithmetic in the same order: bit-identical outputs. SPIDER_GEMV_SCHED is read once, at the first use;
+ * SPIDER_GEMV_HOIST=0 selects schedule 0 without its weight hoist. Returns the previous setting. */
+int spider_set_gemv_sched(int sched);
 /* Tuning / test aid: split-K combine of the weight-stationary streaming conv (w_tiled = 2): 1 = inside the launch by the last-arriving
  * block of a strip (default), 0 = partial slabs + the reduce kernel (SPIDER_WS_INLAUNCH is read at the first such launch). Both forms sum
  * the slabs in split order: bit-identical outputs. The arrival counters live in the 4096 bytes behind the declared workspace: ONE stream

@@ -159,10 +159,30 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16_t* __restrict__
 //   epilogue: (+bias) -> bf16 -> (+res -> bf16);  GATEUP: W holds [gate rows | up rows] (2*N rows) and
 //         out[b,n] = bf16(bf16(silu(bf16(g))) * bf16(u))     (modeling_llama3.py:197-199)
 // Each wave owns R output columns and streams their weight rows with 16-B loads (1 KiB per wave
-// instruction), U chunks deep; activations are staged once per block in LDS as bf16 (XLDS) or, when
-// NB*K*2 bytes exceed the LDS budget, re-read through L2.
+// instruction); activations are staged once per block in LDS as bf16 (XLDS) or, when NB*K*2 bytes
+// exceed the LDS budget, re-read through L2.
+//
+// SCHED picks how the block's memory requests are ordered; the arithmetic (every FMA, every rounding, every
+// reduction) is the same in all three, so their outputs are bit-identical:
+//   0  one request at a time: U chunks per row requested before the prologue (`hoist`), the prologue loads one x
+//      vector per thread and waits for it (twice over in the normalised form, which reads x again and norm_w only
+//      after the sum of squares), and the k loop requests a chunk set only after the previous one is consumed.
+//   2  one trip for the prologue: a thread requests its first GEMV_STAGE_CAP (4 or 6) vectors of x (x and norm_w in the
+//      normalised form) FIRST, then the hoisted weight chunks, so that the wait for x leaves the weight loads in
+//      flight (vmcnt retires in order); x stays in registers from the sum of squares to the normalise pass. Longer
+//      rows go on in batches of GEMV_STAGE_CAP. Loads are unconditional on clamped addresses (a load under a
+//      per-lane branch makes the compiler drain the queue); only the FMAs are predicated by k < K.
+//      With 8 waves per block (NWB = 8: the long-K form, the down projection) the k loop holds two register sets:
+//      set i+1 is requested before set i is consumed, so the wait in front of the FMAs is a counted one.
+//   1  as 2, for rows of <= 8 chunks (K <= 4096) and NR*NB <= 2 (qkv, o): EVERY chunk of the row is requested
+//      before the prologue -- the weight stream is one round trip that overlaps the staging -- and no k loop is left.
+// spider_set_gemv_sched / SPIDER_GEMV_SCHED choose between 0 and {1, 2} (gemv_dispatch picks 1 where it applies).
 // ----------------------------------------------------------------------------------------------
-template <int NB, int R, bool GATEUP, bool XLDS, int NWB = 4>
+// 16-byte vectors a thread keeps in flight while it stages the activations (SCHED 1 / 2): one batch covers K <= 8192 (plain) or
+// 4096 (normalised: half of them are norm_w) with 4 waves per block, K <= 24576 with 8 (the down projection asks for 5)
+constexpr int GEMV_STAGE_CAP(int nwb) { return nwb == 8 ? 6 : 4; }
+
+template <int NB, int R, bool GATEUP, bool XLDS, int NWB = 4, int SCHED = 0>
 __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict__ W, const bf16_t* __restrict__ x,
                                                    bf16_t* __restrict__ out, const bf16_t* __restrict__ bias,
                                                    const bf16_t* __restrict__ res, const bf16_t* __restrict__ norm_w,
@@ -170,7 +190,8 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* xs = reinterpret_cast<bf16_t*>(smem);  // [NB][K] when XLDS
     __shared__ float red[NWB];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // SCHED 1 / 2: the wave index as a scalar, so that the row pointers live in SGPRs and a weight load costs one address VGPR
+    const int lane = threadIdx.x & 63, wave = SCHED ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     constexpr int NR = GATEUP ? 2 * R : R;  // weight rows per wave
     constexpr int U = (NR * NB <= 4) ? 4 : 2;  // chunks in flight per row
 
@@ -185,55 +206,162 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
         wrow[r] = W + (size_t)n * K;
         if (GATEUP) wrow[R + r] = W + (size_t)(N + n) * K;
     }
-    u32x4 w0[U][NR];
-    if (hoist) {
+    constexpr int H = SCHED == 1 ? 8 : U;   // chunks per row requested before the prologue (SCHED 1: the whole row)
+    u32x4 w0[H][NR];
+    if constexpr (SCHED == 0) {
+        if (hoist) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = lane * 8 + u * 512;
-            if (k < K) {
+            for (int u = 0; u < U; ++u) {
+                const int k = lane * 8 + u * 512;
+                if (k < K) {
 #pragma unroll
-                for (int r = 0; r < NR; ++r)
-                    w0[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + k));
+                    for (int r = 0; r < NR; ++r)
+                        w0[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + k));
+                }
             }
         }
-    }
 
-    if (XLDS) {
-        const int nv = K / 8;
-        for (int b = 0; b < NB; ++b) {
-            const u32x4* xv = reinterpret_cast<const u32x4*>(x + (size_t)b * K);
-            u32x4* sv = reinterpret_cast<u32x4*>(xs + (size_t)b * K);
-            if (norm_w) {
-                float ss = 0.f;
-                for (int i = threadIdx.x; i < nv; i += NWB * 64) {
-                    u32x4 a = xv[i];
-                    uint32_t aw[4] = {a.x, a.y, a.z, a.w};
+        if (XLDS) {
+            const int nv = K / 8;
+            for (int b = 0; b < NB; ++b) {
+                const u32x4* xv = reinterpret_cast<const u32x4*>(x + (size_t)b * K);
+                u32x4* sv = reinterpret_cast<u32x4*>(xs + (size_t)b * K);
+                if (norm_w) {
+                    float ss = 0.f;
+                    for (int i = threadIdx.x; i < nv; i += NWB * 64) {
+                        u32x4 a = xv[i];
+                        uint32_t aw[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            float lo = bf16lo_to_f32(aw[j]), hi = bf16hi_to_f32(aw[j]);
+                            ss += lo * lo + hi * hi;
+                        }
+                    }
+                    const float rs = rsqrtf(block_sum<NWB>(ss, red) / (float)K + eps);
+                    const u32x4* wv = reinterpret_cast<const u32x4*>(norm_w);
+                    for (int i = threadIdx.x; i < nv; i += NWB * 64) {
+                        u32x4 a = xv[i], wq = wv[i];
+                        uint32_t aw[4] = {a.x, a.y, a.z, a.w}, ww[4] = {wq.x, wq.y, wq.z, wq.w}, o[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            float lo = bf16_to_f32(f32_to_bf16(bf16lo_to_f32(aw[j]) * rs)) * bf16lo_to_f32(ww[j]);
+                            float hi = bf16_to_f32(f32_to_bf16(bf16hi_to_f32(aw[j]) * rs)) * bf16hi_to_f32(ww[j]);
+                            o[j] = pack_bf16x2(lo, hi);
+                        }
+                        u32x4 ov;
+                        ov.x = o[0]; ov.y = o[1]; ov.z = o[2]; ov.w = o[3];
+                        sv[i] = ov;
+                    }
+                } else {
+                    for (int i = threadIdx.x; i < nv; i += NWB * 64) sv[i] = xv[i];
+                }
+            }
+            __syncthreads();
+        }
+
+    } else {
+        // Branch-free staging: every load goes to a clamped index, a vector past the end of the row counts as zero in the sum of
+        // squares (adding +0 is exact) and is stored, normalised or not, to the clamped slot, where every writer has the same value.
+        constexpr int NT = NWB * 64, CAP = GEMV_STAGE_CAP(NWB), CH = CAP / 2;
+        const int nv = K / 8, t0 = threadIdx.x;
+        const u32x4* wv = reinterpret_cast<const u32x4*>(norm_w);
+        u32x4 st[CAP];
+        auto issue_x = [&](const u32x4* xv, int i0) {     // plain form: CAP vectors of x
+#pragma unroll
+            for (int c = 0; c < CAP; ++c) st[c] = xv[min(i0 + c * NT, nv - 1)];
+        };
+        auto issue_xw = [&](const u32x4* xv, int i0) {    // normalised form: CH vectors of x, then the same CH of norm_w
+#pragma unroll
+            for (int c = 0; c < CH; ++c) st[c] = xv[min(i0 + c * NT, nv - 1)];
+#pragma unroll
+            for (int c = 0; c < CH; ++c) st[CH + c] = wv[min(i0 + c * NT, nv - 1)];
+        };
+        auto store_x = [&](u32x4* sv, int i0) {
+#pragma unroll
+            for (int c = 0; c < CAP; ++c) sv[min(i0 + c * NT, nv - 1)] = st[c];
+        };
+        auto sumsq = [&](float ss, int i0, int n) {
+#pragma unroll
+            for (int c = 0; c < CAP; ++c) {
+                if (c < n) {
+                    const bool in = i0 + c * NT < nv;
+                    uint32_t aw[4] = {in ? st[c].x : 0u, in ? st[c].y : 0u, in ? st[c].z : 0u, in ? st[c].w : 0u};
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         float lo = bf16lo_to_f32(aw[j]), hi = bf16hi_to_f32(aw[j]);
                         ss += lo * lo + hi * hi;
                     }
                 }
-                const float rs = rsqrtf(block_sum<NWB>(ss, red) / (float)K + eps);
-                const u32x4* wv = reinterpret_cast<const u32x4*>(norm_w);
-                for (int i = threadIdx.x; i < nv; i += NWB * 64) {
-                    u32x4 a = xv[i], wq = wv[i];
-                    uint32_t aw[4] = {a.x, a.y, a.z, a.w}, ww[4] = {wq.x, wq.y, wq.z, wq.w}, o[4];
+            }
+            return ss;
+        };
+        auto norm_store = [&](u32x4* sv, int i0, float rs) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float lo = bf16_to_f32(f32_to_bf16(bf16lo_to_f32(aw[j]) * rs)) * bf16lo_to_f32(ww[j]);
-                        float hi = bf16_to_f32(f32_to_bf16(bf16hi_to_f32(aw[j]) * rs)) * bf16hi_to_f32(ww[j]);
-                        o[j] = pack_bf16x2(lo, hi);
-                    }
-                    u32x4 ov;
-                    ov.x = o[0]; ov.y = o[1]; ov.z = o[2]; ov.w = o[3];
-                    sv[i] = ov;
+            for (int c = 0; c < CH; ++c) {
+                const u32x4 a = st[c], wq = st[CH + c];
+                uint32_t aw[4] = {a.x, a.y, a.z, a.w}, ww[4] = {wq.x, wq.y, wq.z, wq.w}, o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float lo = bf16_to_f32(f32_to_bf16(bf16lo_to_f32(aw[j]) * rs)) * bf16lo_to_f32(ww[j]);
+                    float hi = bf16_to_f32(f32_to_bf16(bf16hi_to_f32(aw[j]) * rs)) * bf16hi_to_f32(ww[j]);
+                    o[j] = pack_bf16x2(lo, hi);
                 }
-            } else {
-                for (int i = threadIdx.x; i < nv; i += NWB * 64) sv[i] = xv[i];
+                u32x4 ov;
+                ov.x = o[0]; ov.y = o[1]; ov.z = o[2]; ov.w = o[3];
+                sv[min(i0 + c * NT, nv - 1)] = ov;
+            }
+        };
+        auto hoist_w = [&]() {
+#pragma unroll
+            for (int u = 0; u < H; ++u) {
+                const int k = lane * 8 + u * 512;
+#pragma unroll
+                for (int r = 0; r < NR; ++r)
+                    w0[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + (unsigned)(k < K ? k : K - 8)));
+            }
+        };
+        // Three straight-line forms, each with the first batch of row 0 requested BEFORE the weights: vmcnt retires in order, so the
+        // wait for that batch leaves the weight loads in flight (any later batch or row waits for them too).
+        const u32x4* xv = reinterpret_cast<const u32x4*>(x);
+        u32x4* sv = reinterpret_cast<u32x4*>(xs);
+        if (!XLDS) {
+            hoist_w();
+        } else if (!norm_w) {
+            issue_x(xv, t0);
+            hoist_w();
+            store_x(sv, t0);
+            // keeps these stores out of the loop below: merged with its stores they would sit behind the loop's wait for ALL loads
+            asm volatile("" ::: "memory");
+            for (int b = 0; b < NB; ++b)
+                for (int i0 = b ? 0 : CAP * NT; i0 < nv; i0 += CAP * NT) {
+                    issue_x(xv + (size_t)b * nv, i0 + t0);
+                    store_x(sv + (size_t)b * nv, i0 + t0);
+                }
+        } else if (nv <= CH * NT) {
+            // the row fits the registers: x is read once and norm_w is requested with it
+            issue_xw(xv, t0);
+            hoist_w();
+            for (int b = 0; b < NB; ++b) {
+                if (b) issue_xw(xv + (size_t)b * nv, t0);
+                const float rs = rsqrtf(block_sum<NWB>(sumsq(0.f, t0, CH), red) / (float)K + eps);
+                norm_store(sv + (size_t)b * nv, t0, rs);
+            }
+        } else {
+            hoist_w();
+            for (int b = 0; b < NB; ++b) {
+                float ss = 0.f;
+                for (int i0 = 0; i0 < nv; i0 += CAP * NT) {
+                    issue_x(xv + (size_t)b * nv, i0 + t0);
+                    ss = sumsq(ss, i0 + t0, CAP);
+                }
+                const float rs = rsqrtf(block_sum<NWB>(ss, red) / (float)K + eps);
+                for (int i0 = 0; i0 < nv; i0 += CH * NT) {
+                    issue_xw(xv + (size_t)b * nv, i0 + t0);
+                    norm_store(sv + (size_t)b * nv, i0 + t0, rs);
+                }
             }
         }
-        __syncthreads();
+        if (XLDS) __syncthreads();
     }
 
     if (col0 >= N) return;
@@ -263,23 +391,106 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
             }
         }
     };
-    int kstart = lane * 8;
-    if (hoist) {
-        fma_w(w0, kstart);
-        kstart += 512 * U;
-    }
-    for (int k0 = kstart; k0 < K; k0 += 512 * U) {
-        u32x4 wq[U][NR];
+    // one chunk of every row of the wave against the staged activations; FULL: no lane is past the end of the row
+    auto fma_chunk = [&](const u32x4 (&wq)[NR], int k, bool full) {
+        if (full || k < K) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = k0 + u * 512;
-            if (k < K) {
+            for (int b = 0; b < NB; ++b) {
+                u32x4 xq = XLDS ? *reinterpret_cast<const u32x4*>(xs + (size_t)b * K + k)
+                                : *reinterpret_cast<const u32x4*>(x + (size_t)b * K + k);
+                const uint32_t xw[4] = {xq.x, xq.y, xq.z, xq.w};
 #pragma unroll
-                for (int r = 0; r < NR; ++r)
-                    wq[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + k));
+                for (int r = 0; r < NR; ++r) {
+                    const uint32_t ww[4] = {wq[r].x, wq[r].y, wq[r].z, wq[r].w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[b][r] = dot2_bf16(ww[j], xw[j], acc[b][r]);
+                }
             }
         }
-        fma_w(wq, k0);
+    };
+    if constexpr (SCHED == 1) {
+        // the whole row is in flight since before the prologue: consume it in k order, each chunk behind a counted wait
+#pragma unroll
+        for (int u = 0; u < H; ++u) fma_chunk(w0[u], lane * 8 + u * 512, false);
+    } else if constexpr (SCHED == 2 && NWB == 8) {
+        // two register sets: set i+1 is requested before set i is consumed
+        constexpr int S = 512 * U;
+        u32x4 w1[U][NR];
+        auto load_set = [&](u32x4 (&wq)[U][NR], int base) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int k = base + lane * 8 + u * 512;
+#pragma unroll
+                for (int r = 0; r < NR; ++r)
+                    wq[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + (unsigned)(k < K ? k : K - 8)));
+            }
+        };
+        auto fma_set = [&](const u32x4 (&wq)[U][NR], int base, bool full) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) fma_chunk(wq[u], base + lane * 8 + u * 512, full);
+        };
+        // sets 0 .. nfull-1 are full and have a successor; set nfull is the last one. The hoisted set is consumed ahead of the loop
+        // (as a loop-carried value it would be copied into the loop's registers, behind a wait for all of it); the loop takes two
+        // sets per trip, so that the sets keep their registers, and has ONE exit, so that the compiler's wait counts see the same
+        // queue on every path.
+        const int nfull = (K - 1) / S;
+        if (nfull == 0) {
+            fma_set(w0, 0, false);
+        } else {
+            load_set(w1, S);
+            fma_set(w0, 0, true);
+            int s = 1;
+            for (; s + 2 <= nfull; s += 2) {
+                // no request for a set moves above the FMAs that read its registers' previous contents
+                __builtin_amdgcn_sched_barrier(0);
+                load_set(w0, (s + 1) * S);
+                fma_set(w1, s * S, true);
+                __builtin_amdgcn_sched_barrier(0);
+                load_set(w1, (s + 2) * S);
+                fma_set(w0, (s + 1) * S, true);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (s < nfull) {
+                load_set(w0, (s + 1) * S);
+                fma_set(w1, s * S, true);
+                fma_set(w0, (s + 1) * S, false);
+            } else {
+                fma_set(w1, s * S, false);
+            }
+        }
+    } else if constexpr (SCHED == 2) {
+        // the k loop of schedule 0 with the hoisted set always there and unconditional loads on clamped addresses
+        fma_w(w0, lane * 8);
+        for (int k0 = lane * 8 + 512 * U; k0 < K; k0 += 512 * U) {
+            u32x4 wq[U][NR];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int k = k0 + u * 512;
+#pragma unroll
+                for (int r = 0; r < NR; ++r)
+                    wq[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + (unsigned)(k < K ? k : K - 8)));
+            }
+            fma_w(wq, k0);
+        }
+    } else {
+        int kstart = lane * 8;
+        if (hoist) {
+            fma_w(w0, kstart);
+            kstart += 512 * U;
+        }
+        for (int k0 = kstart; k0 < K; k0 += 512 * U) {
+            u32x4 wq[U][NR];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int k = k0 + u * 512;
+                if (k < K) {
+#pragma unroll
+                    for (int r = 0; r < NR; ++r)
+                        wq[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + k));
+                }
+            }
+            fma_w(wq, k0);
+        }
     }
 #pragma unroll
     for (int b = 0; b < NB; ++b)
@@ -1368,13 +1579,28 @@ __global__ __launch_bounds__(NW * 64) void skinny_fm_kernel(const bf16_t* __rest
     }
 }
 
+// schedule of gemv_kernel: 0 = SCHED 0 everywhere, 1 = SCHED 1 / 2 (-1: SPIDER_GEMV_SCHED not read yet; default 1)
+static int g_gemv_sched = -1;
+static int gemv_sched() {
+    if (g_gemv_sched < 0) { const char* e = getenv("SPIDER_GEMV_SCHED"); g_gemv_sched = e ? (atoi(e) != 0) : 1; }
+    return g_gemv_sched;
+}
+
 #define GEMV_ARGS (const bf16_t*)W, (const bf16_t*)x, (bf16_t*)out, (const bf16_t*)bias, (const bf16_t*)res, (const bf16_t*)norm_w, eps, N, K, hoist
 // wide8: 8 waves per block share one LDS copy of the activations (long-K projections: the 38 KB copy of a K = 18944 vector per
 // 4-row block is 25 % of the block's weight bytes and caps the resident waves per CU)
+// sched: the SCHED of gemv_kernel (1 only where the instantiation exists: not gate/up, R * NB <= 2, activations in LDS, 4 waves)
 #define GEMV_LAUNCH(NB_, R_, GU_, XL_)                                                                         \
     do {                                                                                                        \
-        if (wide8) gemv_kernel<NB_, R_, GU_, XL_, 8><<<(N + 8 * R_ - 1) / (8 * R_), 512, XL_ ? (size_t)NB_ * K * 2 : 0, (hipStream_t)stream>>>(GEMV_ARGS); \
-        else gemv_kernel<NB_, R_, GU_, XL_, 4><<<grid, 256, XL_ ? (size_t)NB_ * K * 2 : 0, (hipStream_t)stream>>>(GEMV_ARGS); \
+        const size_t lds_ = XL_ ? (size_t)NB_ * K * 2 : 0;                                                      \
+        constexpr bool ROW_ = !GU_ && R_ * NB_ <= 2 && XL_;                                                   \
+        if (wide8) {                                                                                            \
+            if (sched) gemv_kernel<NB_, R_, GU_, XL_, 8, 2><<<(N + 8 * R_ - 1) / (8 * R_), 512, lds_, (hipStream_t)stream>>>(GEMV_ARGS); \
+            else gemv_kernel<NB_, R_, GU_, XL_, 8><<<(N + 8 * R_ - 1) / (8 * R_), 512, lds_, (hipStream_t)stream>>>(GEMV_ARGS); \
+        } else if (sched == 1 && ROW_) {                                                                        \
+            if constexpr (ROW_) gemv_kernel<NB_, R_, GU_, XL_, 4, 1><<<grid, 256, lds_, (hipStream_t)stream>>>(GEMV_ARGS); \
+        } else if (sched) gemv_kernel<NB_, R_, GU_, XL_, 4, 2><<<grid, 256, lds_, (hipStream_t)stream>>>(GEMV_ARGS); \
+        else gemv_kernel<NB_, R_, GU_, XL_, 4><<<grid, 256, lds_, (hipStream_t)stream>>>(GEMV_ARGS);            \
     } while (0)
 
 static int gemv_env_r() {
@@ -1402,6 +1628,9 @@ static int gemv_dispatch(const void* W, const void* x, void* out, const void* bi
     const int grid = (N + 4 * R - 1) / (4 * R);
     static const int wide_env = [] { const char* e = getenv("SPIDER_GEMV_WIDE8"); return e ? atoi(e) : -1; }();
     const bool wide8 = wide_env >= 0 ? wide_env != 0 : (!GU && K >= 8192 && NB == 1);
+    // schedule: SPIDER_GEMV_HOIST=0 keeps its meaning (no weight request before the prologue), which only SCHED 0 has; otherwise
+    // SCHED 1 (the whole row in flight) where the row is <= 8 chunks, SCHED 2 elsewhere
+    const int sched = !(hoist && gemv_sched()) ? 0 : (K <= 4096 ? 1 : 2);
 #define GEMV_PICK(R_)                                   \
     do {                                                \
         if (xlds) GEMV_LAUNCH(NB, R_, GU, true);        \
@@ -1451,6 +1680,14 @@ static int g_attn_inline = -1;
 // C ABI
 // ==============================================================================================
 extern "C" {
+
+// schedule of the decode GEMVs (gemv_kernel SCHED): 0 = one memory request at a time, 1 = one trip per block (default);
+// returns the previous setting. Outputs are bit-identical.
+int spider_set_gemv_sched(int sched) {
+    const int prev = gemv_sched();
+    g_gemv_sched = sched != 0;
+    return prev;
+}
 
 // 1 / 2: the split-KV combine of spider_attn_decode_fused_bf16 is done by the last-arriving block of the attention launch itself (1: acq_rel
 // ticket; 2: write-through partials, relaxed ticket, sc1 loads -- no fence); 0: by the separate combine launch; returns the previous
