@@ -101,6 +101,25 @@ int spider_beam_select_f32(const float* ws_ms, const float* ws_val, const int* w
 int spider_kv_row_gather_bf16(void* k_cache, void* v_cache, void* k_tmp, void* v_tmp, const int* src_beam, const int* kv_beg,
                               const int* kv_end, int K, int R, int layers, int rows_alloc, int n_kv, int T, int d, void* stream);
 
+/* Seeded sampling step (transformers' do_sample=True as conversation.py:151-173 drives it: logits processors, temperature, top-k,
+ * top-p, one draw), two launches behind the lm_head. nslice = ceil(V / 4096); every parameter is read from device memory when the
+ * kernel runs: temperature, top_p float [1], top_k int [1] (1 ... 64), seed uint32 [2] (low, high word), row0 int [1] (absolute
+ * index of row 0 in the call), n_hist int [rows] (tokens generated so far = the step).
+ * spider_sample_partial_bf16: per row of raw bf16 logits [rows, V] and slice of 4096 tokens, the logits processors of
+ *   spider_lm_head_argmax_proc_bf16 (same buffers, same fp32 arithmetic; seen = ban = NULL: none) and the slice's top_k best
+ *   (value, token) into ws_val / ws_tok [rows, nslice, 64] (value descending, token ascending; token -1 past the slice's tokens).
+ * spider_sample_select_f32: per row the top_k candidates in that order (rank 0 ...; exactly top_k, ties at the cut go to the lower
+ *   ids), p_j = expf(x_j / T - x_0 / T) (0 for x_j = -inf), P = sum in rank order; rank j kept iff the mass before it < top_p * P
+ *   (at least rank 0), S = kept mass; u = ((x >> 9) + 0.5) * 2^-23 with x the first word of Philox4x32-10 at counter
+ *   (n_hist[row], row0 + row, 0, 0), key seed; next_ids[row] = first kept rank with u * S < p_0 + ... + p_j, else the last kept.
+ *   Also written: cand_tok / cand_p [rows, 64] (-1 / 0 past top_k), n_keep [rows], u [rows]. */
+int spider_sample_partial_bf16(const void* logits, const void* seen, const void* ban, const float* penalty, const int* min_new,
+                               const int* eos_ids, const int* n_eos, const int* n_hist, const int* top_k, float* ws_val,
+                               int* ws_tok, int rows, int V, int nslice, void* stream);
+int spider_sample_select_f32(const float* ws_val, const int* ws_tok, const float* temperature, const float* top_p, const int* top_k,
+                             const void* seed, const int* row0, const int* n_hist, int* next_ids, int* cand_tok, float* cand_p,
+                             int* n_keep, float* u, int rows, int V, int nslice, void* stream);
+
 /* apply_rotary_pos_emb (modeling_llama3.py:150-183; modeling_llama.py:116-123) on q,k of a fused QKV
  * projection + KV-cache append (modeling_llama.py:190-193). qkv [B*S,(n_q+2n_kv)*d]; cos_sin fp32
  * [max_pos, d] = [cos(d/2) | sin(d/2)]; q_out [B*S,n_q,d]; caches [B,n_kv,T_max,d]. */

@@ -10,6 +10,7 @@
 //                 launch writes, whatever the map (duplicates, cycles); rows that keep their history are skipped by both.
 // Orderings are total: the reductions compare 64-bit keys (order-preserving bits of the fp32 value, then the inverted index).
 #include "common.hpp"
+#include "select.hpp"
 
 using namespace spider;
 
@@ -19,38 +20,6 @@ constexpr int BEAM_SLICE = 4096;     // tokens per block of the partial reductio
 constexpr int BEAM_MAX_C = 32;       // continuations kept per batch row
 constexpr int BEAM_MAX_K = 8;
 constexpr int BEAM_MAX_EOS = 8;
-
-typedef unsigned long long u64;
-
-// fp32 -> uint32 whose unsigned order is the float order (-inf lowest); -0 was canonicalised to +0 by the caller
-__device__ __forceinline__ uint32_t f32_ord(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord_f32(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-// larger key = better: value first, then the LOWER index. Key 0 is "nothing" (a real key has a non-zero value half or index half).
-__device__ __forceinline__ u64 make_key(float v, uint32_t idx) { return ((u64)f32_ord(v + 0.f) << 32) | (u64)(0xFFFFFFFFu - idx); }
-
-__device__ __forceinline__ u64 wave_max_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 t = __shfl_xor(v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-// block of 4 waves; `red` = 4 keys of LDS that nobody touches until the next barrier after this call's
-__device__ __forceinline__ u64 block_max_u64(u64 v, u64* red) {
-    v = wave_max_u64(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 r = red[0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i) r = red[i] > r ? red[i] : r;
-    return r;
-}
 
 __global__ __launch_bounds__(256) void beam_partial_kernel(const bf16_t* __restrict__ logits, float* __restrict__ ws_ms,
                                                            float* __restrict__ ws_val, int* __restrict__ ws_tok, int V, int C,
@@ -95,8 +64,7 @@ __global__ __launch_bounds__(256) void beam_partial_kernel(const bf16_t* __restr
         ws_ms[((size_t)r * nslice + s) * 2] = ms;
         ws_ms[((size_t)r * nslice + s) * 2 + 1] = e;
     }
-    // the slice's C best, one per round: a thread offers its best key below the key taken last (keys are unique, so "below the
-    // last winner" is "not taken yet") and only the winner's owner looks through its 16 values again
+    // the slice's C best, one per round (block_select_best): the winner's owner looks through its 16 values again
     auto scan = [&](u64 limit) {
         u64 best = 0;
 #pragma unroll
@@ -107,17 +75,14 @@ __global__ __launch_bounds__(256) void beam_partial_kernel(const bf16_t* __restr
         }
         return best;
     };
-    u64 mine = scan(~0ull);
     float* ov = ws_val + ((size_t)r * nslice + s) * C;
     int* ot = ws_tok + ((size_t)r * nslice + s) * C;
-    for (int c = 0; c < C; ++c) {
-        const u64 w = block_max_u64(mine, redk[c & 1]);
+    block_select_best(C, redk, scan, [&](int c, u64 w) {
         if (tid == 0) {
-            ov[c] = w ? ord_f32((uint32_t)(w >> 32)) : -INFINITY;
-            ot[c] = w ? (int)(0xFFFFFFFFu - (uint32_t)w) : -1;        // a slice with fewer than C tokens: token -1
+            ov[c] = w ? key_value(w) : -INFINITY;
+            ot[c] = w ? (int)key_index(w) : -1;        // a slice with fewer than C tokens: token -1
         }
-        if (w && mine == w) mine = scan(w);
-    }
+    });
 }
 
 __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restrict__ ws_ms, const float* __restrict__ ws_val,
@@ -165,17 +130,14 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
         }
         return best;
     };
-    u64 mine = scan(~0ull);
-    for (int c = 0; c < C; ++c) {
-        const u64 w = block_max_u64(mine, redk[c & 1]);
+    block_select_best(C, redk, scan, [&](int c, u64 w) {
         if (tid == 0) {
-            const uint32_t flat = 0xFFFFFFFFu - (uint32_t)w;
-            c_score[c] = w ? ord_f32((uint32_t)(w >> 32)) : -INFINITY;
+            const uint32_t flat = key_index(w);
+            c_score[c] = w ? key_value(w) : -INFINITY;
             c_beam[c] = w ? (int)(flat / (uint32_t)V) : 0;
             c_tok[c] = w ? (int)(flat % (uint32_t)V) : 0;
         }
-        if (w && mine == w) mine = scan(w);
-    }
+    });
     __syncthreads();
     const int step = n_hist[b * K];
     if (tid < C && step >= 0 && step < cap) {

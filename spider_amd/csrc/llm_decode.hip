@@ -12,6 +12,7 @@
 // Layouts: activations [B, H] bf16 row-major; weights [N, K] bf16 row-major (nn.Linear layout, never
 // transposed); KV cache [B, n_kv, T_max, d] bf16. All reductions accumulate in fp32.
 #include "common.hpp"
+#include "select.hpp"
 #include <stdlib.h>
 
 using namespace spider;
@@ -528,44 +529,9 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
 // partial. Stage 2: one block reduces the partials per batch row. Ties -> lowest token id.
 // ----------------------------------------------------------------------------------------------
 //
-// PROC forms (spider_lm_head_argmax_proc_bf16 / _fm_proc_bf16): HF's deterministic logits processors in the arg-max epilogue,
-// applied to the bf16-rounded logit widened to fp32 -- the value transformers hands to its processors
-// (generation/logits_process.py: RepetitionPenalty, NoBadWords / SuppressTokens, MinLength / MinNewTokensLength):
-//   bit n of seen[b] set:          lv = lv < 0 ? lv * p : lv / p     (fp32, IEEE division)
-//   bit n of ban[b] set:           lv = -inf
-//   n an EOS id, n_hist[b] < min_new:  lv = -inf
-// Every parameter lives in device memory (one captured decode graph serves requests with different values); the bitmaps are
-// uint32 [B, words], words = ceil(V / 32), read with per-lane (vector) loads. The optional logits output stays the RAW logit.
-struct LmProc {
-    const uint32_t* seen;     // [B, words] ids already in the row's sequence (prompt ids of an input_ids call + generated ids)
-    const uint32_t* ban;      // [B, words] suppress_tokens / single-token bad_words_ids
-    const float* penalty;     // [1]
-    const int* min_new;       // [1] EOS is banned while n_hist[b] < min_new
-    const int* eos_ids;       // [8]
-    const int* n_eos;         // [1] 0 ... 8
-    const int* n_hist;        // [B] tokens generated so far
-    int words;
-};
-
-// bit 0: row n of sequence b is in `seen`; bit 1: it is banned (ban bitmap, or an EOS id before min_new tokens)
-__device__ __forceinline__ uint32_t lm_proc_flags(const LmProc& pr, int b, int n) {
-    const size_t w = (size_t)b * pr.words + (n >> 5);
-    const uint32_t bit = 1u << (n & 31);
-    uint32_t f = (pr.seen[w] & bit) ? 1u : 0u;
-    if (pr.ban[w] & bit) f |= 2u;
-    if (pr.n_hist[b] < pr.min_new[0]) {
-        const int ne = min(pr.n_eos[0], 8);
-        for (int e = 0; e < ne; ++e)
-            if (pr.eos_ids[e] == n) f |= 2u;
-    }
-    return f;
-}
-
-__device__ __forceinline__ float lm_proc_apply(float lv, uint32_t flags, float p) {
-    if (flags & 1u) lv = lv < 0.f ? lv * p : __fdiv_rn(lv, p);
-    if (flags & 2u) lv = -INFINITY;
-    return lv;
-}
+// PROC forms (spider_lm_head_argmax_proc_bf16 / _fm_proc_bf16): HF's deterministic logits processors in the arg-max epilogue
+// (LmProc, lm_proc_flags, lm_proc_apply of select.hpp, shared with the sampling kernels). The optional logits output stays the
+// RAW logit.
 
 template <int NB, int R, bool PROC = false>
 __global__ __launch_bounds__(256) void lmhead_partial_kernel(const bf16_t* __restrict__ W, const bf16_t* __restrict__ x,

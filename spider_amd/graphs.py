@@ -4,12 +4,32 @@ signature; inputs are copied into static buffers, the result is returned as a fr
 next replay). SPIDER_NO_GRAPHS=1 runs everything eagerly."""
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 from typing import Callable, Dict, Tuple
 
 import torch
 
 _DISABLED = os.environ.get("SPIDER_NO_GRAPHS", "0") == "1"
+
+
+@contextlib.contextmanager
+def capture(graph: "torch.cuda.CUDAGraph", **kw):
+    """`torch.cuda.graph(graph)` with Python's cyclic garbage collected first and the collector off while the stream captures.
+    An engine dropped by its owner can wait for the collector (the GraphRunner lambdas of the CLIP / VAE engines close over their
+    engine), and with it its captured graphs; torch.cuda.graph no longer collects on entry. A collection that starts inside a
+    capture then destroys those graphs there, the ROCm build of torch synchronises the device in that destructor, a device
+    synchronisation is illegal while a stream captures, and the error leaves a destructor: the process aborts."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class GraphRunner:
@@ -33,7 +53,7 @@ class GraphRunner:
                 self.fn(*static_in)                      # warm-up outside capture (lazy allocations, first-use setup)
             torch.cuda.current_stream(dev).wait_stream(s)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with capture(g):
                 out = self.fn(*static_in)
             ent = (g, static_in, out)
             self.cache[k] = ent

@@ -25,6 +25,10 @@ Beam search (num_beams 2..8, with length_penalty / early_stopping / num_return_s
 `_beam_search` -- log-softmax of the raw logits, the best continuations of a batch row's K beams, the KV-cache reorder -- is three
 launches behind the lm_head inside the captured decode graph (csrc/beam_search.hip); `beam_finalize_host` replays HF's
 finished-hypotheses bookkeeping on the trace the device wrote. num_beams=1 is the greedy path, unchanged.
+
+Sampling (do_sample=True with temperature / top_k 1..64 / top_p / seed, as conversation.py:151-173 calls generate): behind the
+raw-logits lm_head two launches (csrc/sample.hip) apply the processors, keep the top_k best, cut the nucleus and draw with a
+counter-based generator, inside the captured decode graph; `sample_token_host` / `sample_uniform_host` are the definition.
 """
 from __future__ import annotations
 
@@ -36,6 +40,7 @@ from typing import Callable, List, Optional, Sequence
 import torch
 
 from . import ops
+from .graphs import capture as capture_graph
 
 BF16 = torch.bfloat16
 
@@ -186,6 +191,94 @@ def process_logits_host(logits: torch.Tensor, seen: torch.Tensor, p: float, ban:
             if 0 <= t < V:
                 lv[:, t] = -math.inf
     return lv
+
+
+SAMPLE_MAX_K = 64       # top_k limit of the sampling kernels (csrc/sample.hip)
+
+
+def resolve_sampling(do_sample, temperature=1.0, top_k=None, top_p=1.0, num_return_sequences=1):
+    """Validate the sampling keywords of `generate` against what the sampling kernels implement and return (temperature, top_k,
+    top_p), or None for do_sample=False (which ignores the three warper arguments, as HF does). The ValueErrors are the ones
+    transformers' TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper raise for the same values; a top_k that switches
+    the filter off (0) or exceeds the kernels' candidate list raises NotImplementedError: the nucleus is taken among at most
+    SAMPLE_MAX_K tokens, a full-vocabulary top-p is not implemented. top_k=None is what transformers' `generate` resolves it to."""
+    if not do_sample:
+        return None
+    if num_return_sequences not in (None, 1):
+        raise NotImplementedError("do_sample=True with num_return_sequences > 1 is not implemented")
+    if temperature is None or (temperature == 1 and not isinstance(temperature, bool)):
+        temperature = 1.0       # HF builds no warper for 1 (the reference's integer default, spider.py:1471-1477)
+    if not isinstance(temperature, float) or not (temperature > 0):
+        raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+    try:
+        top_p = float(top_p)
+    except (TypeError, ValueError):
+        raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}") from None
+    if not (0 < top_p <= 1.0):
+        raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
+    if top_k is None:
+        top_k = 50
+        try:
+            from transformers import GenerationConfig
+            top_k = GenerationConfig._get_default_generation_params().get("top_k", top_k)
+        except (ImportError, AttributeError):
+            pass
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+        raise ValueError(f"`top_k` has to be a strictly positive integer, but is {top_k}")
+    if top_k == 0 or top_k > SAMPLE_MAX_K:
+        raise NotImplementedError(f"top_k={top_k}: sampling keeps between 1 and {SAMPLE_MAX_K} candidates per step (top_k = 0 switches "
+                                  "HF's filter off; a full-vocabulary nucleus is not implemented)")
+    return temperature, top_k, top_p
+
+
+def resolve_seed(seed) -> int:
+    """The 64-bit seed of a sampling request: an int as given; None draws 63 bits from torch's default CPU generator, so
+    torch.manual_seed makes a run reproducible."""
+    if seed is None:
+        return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"`seed` has to be an integer or None, but is {seed}")
+    return seed & (2 ** 64 - 1)
+
+
+def sample_uniform_host(seed: int, row: int, step: int) -> float:
+    """The uniform of the sampling kernels for (seed, absolute row of the call, number of tokens the row has generated so far):
+    Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) at counter (step, row, 0, 0); u = ((out[0] >> 9) + 0.5) * 2^-23: 24
+    significant bits, so exact in fp32 and strictly inside (0, 1)."""
+    M = 0xFFFFFFFF
+    c = [step & M, row & M, 0, 0]
+    k0, k1 = seed & M, (seed >> 32) & M
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & M, (p0 >> 32) ^ c[3] ^ k1, p0 & M]
+        k0, k1 = (k0 + 0x9E3779B9) & M, (k1 + 0xBB67AE85) & M
+    return ((c[0] >> 9) + 0.5) * 2.0 ** -23
+
+
+def sample_token_host(x: torch.Tensor, temperature: float, top_k: int, top_p: float, u: float) -> dict:
+    """Host restatement in fp64 of the sampling step (csrc/sample.hip) for ONE row of processed logits x [V] (fp32, the result of
+    `process_logits_host`):
+      candidates  the top_k tokens by (x descending, token id ascending) = rank 0 .. top_k - 1. EXACTLY top_k: HF's TopKLogitsWarper
+                  keeps every token that ties with the k-th value, here the lower ids win
+      p           p_j = exp(x_j / T - x_0 / T), 0 where x_j = -inf; P = their sum
+      n_keep      rank j is kept iff the mass before it < top_p * P (HF's TopPLogitsWarper on the survivors of top-k); at least 1
+      token       the first kept rank j with u * S < p_0 + ... + p_j, S = the kept mass; rank n_keep - 1 if rounding leaves none
+    Returns dict(tokens [k] int64, x [k] fp32, p [k] fp64, cum [k] fp64 (cum[j] = p_0 + ... + p_j), n_keep, S, rank, token)."""
+    x = x.detach().float().cpu().view(-1)
+    k = min(int(top_k), x.numel())
+    xs, idx = torch.sort(x, descending=True, stable=True)        # stable: equal values keep the ascending ids
+    xs, idx = xs[:k], idx[:k]
+    y = xs.double() / float(temperature)
+    p = torch.where(torch.isinf(xs) & (xs < 0), torch.zeros_like(y), torch.exp(y - y[0]))
+    p = torch.nan_to_num(p, nan=0.0)        # a row that is all -inf
+    cum = p.cumsum(0)
+    P = float(cum[-1])
+    before = cum - p
+    n_keep = max(1, int((before < float(top_p) * P).sum()))
+    S = float(cum[n_keep - 1])
+    hit = (float(u) * S < cum[:n_keep]).nonzero()
+    rank = int(hit[0]) if hit.numel() else n_keep - 1
+    return dict(tokens=idx, x=xs, p=p, cum=cum, n_keep=n_keep, S=S, rank=rank, token=int(idx[rank]))
 
 
 def finalize_greedy(tokens: torch.Tensor, eos: Optional[List[int]], pad: Optional[int], stopping_criteria,
@@ -544,21 +637,24 @@ class LlamaEngine:
 
     @staticmethod
     def _state_key(B: int, output_hidden_states: bool, return_logits: bool, cache_set: int, processed: bool = False,
-                   beam: Optional[tuple] = None) -> tuple:
+                   beam: Optional[tuple] = None, sample: bool = False) -> tuple:
         """key of a decode state + captured graph; requests with logits processors have their own (one more element), and so have
-        beam-search requests (B = batch rows; beam = (num_beams, continuations kept per step): three more elements)"""
+        beam-search requests (B = batch rows; beam = (num_beams, continuations kept per step): three more elements) and sampling
+        requests ("sample" as the last element, behind the processors' one)"""
         key = (int(B), bool(output_hidden_states), bool(return_logits), int(cache_set))
         if beam is not None:
             return key + ("beam", int(beam[0]), int(beam[1]))
-        return key + (True,) if processed else key
+        key = key + (True,) if processed else key
+        return key + ("sample",) if sample else key
 
     def would_capture(self, B: int, output_hidden_states: bool = False, return_logits: bool = False, cache_set: int = 0,
-                      processed: bool = False, num_beams: int = 1, n_eos: int = 0) -> bool:
+                      processed: bool = False, num_beams: int = 1, n_eos: int = 0, do_sample: bool = False) -> bool:
         """True when the decode loop of such a request would capture its hipGraph (state missing or not captured yet).
         processed: a request with non-neutral logits processors (repetition_penalty != 1, a ban set, or EOS banned at first)
-        num_beams > 1: a beam-search request of B batch rows with n_eos EOS ids (they size the continuations kept per step)"""
+        num_beams > 1: a beam-search request of B batch rows with n_eos EOS ids (they size the continuations kept per step)
+        do_sample: a sampling request (one graph serves every temperature / top_k / top_p / seed)"""
         beam = (num_beams, max(2, 1 + n_eos) * num_beams) if num_beams > 1 else None
-        ent = self._graphs.get(self._state_key(B, output_hidden_states, return_logits, cache_set, processed, beam))
+        ent = self._graphs.get(self._state_key(B, output_hidden_states, return_logits, cache_set, processed, beam, bool(do_sample)))
         return ent is None or ent[1] is None
 
     def _vocab_changed(self):
@@ -645,7 +741,15 @@ class LlamaEngine:
             self._beam_step(st)
             return
         proc = st.get("proc")      # logits processors in the arg-max epilogue (their parameters are read from the state's buffers)
-        if proc is not None and fm:
+        if st.get("sample") is not None:    # sampling: the raw logits go to the sampling step, which applies the processors itself
+            if fm:
+                ops.lm_head_argmax_fm(self.lm_head_fm, h, c.vocab, out_ids=st["sample"]["lm_ids"], ws=st["lm_ws"], logits=st["logits"],
+                                      norm_eps=c.eps)
+            else:
+                ops.lm_head_argmax(self.lm_head, h, norm_w=self.norm, eps=c.eps, out_ids=st["sample"]["lm_ids"], ws=st["lm_ws"],
+                                   logits=st["logits"])
+            self._sample_step(st)
+        elif proc is not None and fm:
             ops.lm_head_argmax_fm_proc(self.lm_head_fm, h, c.vocab, proc, out_ids=st["next_ids"], ws=st["lm_ws"],
                                        logits=st.get("logits"), norm_eps=c.eps)
         elif proc is not None:
@@ -666,6 +770,12 @@ class LlamaEngine:
         else:
             ops.decode_advance(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["hist"], st["n_hist"])
 
+    def _sample_step(self, st: dict):
+        """Behind the raw-logits lm_head of a sampling step (graph-capturable, no host sync): st["next_ids"] = one draw per row from
+        the processed, temperature / top-k / top-p warped distribution, at step n_hist[row] (`sample_token_host`)."""
+        ops.sample_partial(st["logits"], st["sample"], st.get("proc"))
+        ops.sample_select(st["sample"], st["n_hist"], st["next_ids"], self.cfg.vocab)
+
     def _beam_step(self, st: dict, reorder: bool = True):
         """Behind the lm_head of a beam-search step (graph-capturable, no host sync): the C best continuations of every batch row go
         to the trace, the first K non-EOS ones become the running beams (scores, tokens), the KV rows follow their source beams and
@@ -682,7 +792,7 @@ class LlamaEngine:
     _PROC_BUFS = ("seen", "ban", "penalty", "min_new", "eos_ids", "n_eos")
 
     def _make_state(self, B: int, want_hidden: bool, want_logits: bool, cache_set: int = 0, processed: bool = False,
-                    beam: Optional[tuple] = None) -> dict:
+                    beam: Optional[tuple] = None, sample: bool = False) -> dict:
         c, dv = self.cfg, self.device
         nq_d = c.n_q * c.head_dim
         # one split-KV block per CU (256): measured on Qwen-7B shapes at T~1.6k: 2.93 / 2.90 / 3.14 ms per token at 32 / 64 / 96 splits
@@ -708,6 +818,8 @@ class LlamaEngine:
             st.update(seen=i32(B, W), ban=i32(B, W), penalty=torch.ones(1, dtype=torch.float32, device=dv), min_new=i32(1),
                       eos_ids=i32(MAX_EOS_IDS), n_eos=i32(1))
             st["proc"] = {k: st[k] for k in self._PROC_BUFS + ("n_hist",)}
+        if sample:      # the parameters, workspace and outputs of the two sampling launches (the logits buffer is always there)
+            st["sample"] = dict(ops.sample_state(B, c.vocab, dv), lm_ids=i32(B))
         if beam is not None:    # B = batch rows * K here. The trace holds max_len steps; the second KV buffer belongs to the cache set
             K, C = beam
             nb = B // K
@@ -736,8 +848,8 @@ class LlamaEngine:
                       use_graph: bool = True, sync_every: int = 1, return_logits: bool = False,
                       position_ids: Optional[torch.Tensor] = None, cache_set: int = 0, repetition_penalty=1.0, min_length=0,
                       min_new_tokens=0, suppress_tokens=None, bad_words_ids=None, length_penalty=1.0, early_stopping=False,
-                      num_return_sequences=1, num_beam_groups=1, constraints=None, force_words_ids=None, _whole_generate=False,
-                      **unused):
+                      num_return_sequences=1, num_beam_groups=1, constraints=None, force_words_ids=None, temperature=1.0,
+                      top_k=None, top_p=1.0, seed=None, _whole_generate=False, _row0=0, **unused):
         """First half of `generate`: the prompt pass (KV cache of `cache_set` filled, first token chosen, decode cursors set), all
         ENQUEUED on the current stream without a host sync; returns a handle for `decode_finish`. Two requests can be in flight on
         two streams when they use different cache sets (prefill of one beside the decode loop of the other: SpiderFreeInfer's
@@ -763,9 +875,16 @@ class LlamaEngine:
         (its decode loop syncs with the host, so there is no handle to return): a direct prefill_begin(num_beams > 1) raises.
         `generate` returns sequences [B * num_return_sequences, ...], with return_dict_in_generate also
         sequences_scores and beam_indices, with return_logits the running beams' raw logits [B * num_beams, n, V]. Sampling, user
-        stopping_criteria, output_hidden_states, non-neutral logits processors, beam groups and constraints raise."""
-        if do_sample and num_beams == 1:
-            raise NotImplementedError("the reference path is greedy: num_beams=1, do_sample=False (spider.py:1471-1477)")
+        stopping_criteria, output_hidden_states, non-neutral logits processors, beam groups and constraints raise.
+        do_sample=True (num_beams = 1; conversation.py:151-173 always asks for it): one seeded draw per row and step from the
+        distribution HF's processors and its temperature / top_k / top_p warpers leave, chosen on the device inside the decode graph
+        (`sample_token_host` is the definition; `resolve_sampling` the accepted ground: top_k 1..64, None = HF's default). Keyword
+        arguments only. The token of row r at step n depends on (seed, r, n) and the logits alone -- not on graph / eager,
+        sync_every, the split path, the cache set or the grouping of more than 8 rows. seed=None draws the seed from torch's default
+        CPU generator (torch.manual_seed makes the call reproducible). do_sample=False ignores the three warper arguments."""
+        sampling = resolve_sampling(do_sample, temperature, top_k, top_p, num_return_sequences) if num_beams == 1 else None
+        if sampling is not None:
+            seed = resolve_seed(seed)
         c, dv = self.cfg, self.device
         gc = getattr(self, "generation_config", None) or {}
         if eos_token_id is None:
@@ -795,7 +914,8 @@ class LlamaEngine:
                 pad_token_id=pad_token_id, output_hidden_states=output_hidden_states, use_graph=use_graph,
                 sync_every=sync_every, return_logits=return_logits, cache_set=cache_set, repetition_penalty=repetition_penalty,
                 min_length=min_length, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
-                bad_words_ids=bad_words_ids), return_dict_in_generate)
+                bad_words_ids=bad_words_ids, **(dict(do_sample=True, temperature=sampling[0], top_k=sampling[1], top_p=sampling[2],
+                                                     seed=seed) if sampling is not None else {})), return_dict_in_generate)
         if embeds_only:
             h0 = inputs_embeds.to(device=dv, dtype=BF16).contiguous()
             B, S = h0.shape[0], h0.shape[1]
@@ -840,12 +960,17 @@ class LlamaEngine:
 
         # decode state (static buffers + captured hipGraph) is cached per (batch, outputs): repeated generate() calls
         # replay the same graph instead of re-capturing ~200 launches
-        skey = self._state_key(B, output_hidden_states, return_logits, cache_set, processed)
+        sample = sampling is not None
+        skey = self._state_key(B, output_hidden_states, return_logits, cache_set, processed, None, sample)
         if skey not in self._graphs:
-            self._graphs[skey] = [self._make_state(B, output_hidden_states, return_logits, cache_set, processed), None]
+            self._graphs[skey] = [self._make_state(B, output_hidden_states, return_logits or sample, cache_set, processed, None,
+                                                   sample), None]
         st = self._graphs[skey][0]
         st["kv_beg"].copy_(kv_beg)
         last = h.view(B, S, -1)[:, -1].contiguous()
+        if sample:      # this request's values; rows of a grouped call keep their absolute index in the call
+            ops.sample_set_params(st["sample"], *sampling, seed, int(_row0))
+            st["n_hist"].zero_()        # step 0: no token generated yet
         if processed:
             # this request's processor parameters and token sets go into the state's buffers (the captured graph reads them there);
             # the penalised set starts as every id of the row's input_ids, pads included -- empty for an inputs_embeds call (HF)
@@ -861,12 +986,18 @@ class LlamaEngine:
                 ops.token_bitmap_set(input_ids.to(torch.int32).contiguous(), st["seen"], c.vocab)
             if ban:
                 ops.token_bitmap_set(torch.tensor(ban, dtype=torch.int32, device=dv)[None].expand(B, -1).contiguous(), st["ban"], c.vocab)
-            ops.lm_head_argmax_proc(self.lm_head, last, st["proc"], norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"],
-                                    ws=st["lm_ws"], logits=st.get("logits"))
-            ops.token_bitmap_set(st["next_ids"].view(B, 1), st["seen"], c.vocab)
-        else:
+            if not sample:
+                ops.lm_head_argmax_proc(self.lm_head, last, st["proc"], norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"],
+                                        ws=st["lm_ws"], logits=st.get("logits"))
+        elif not sample:
             ops.lm_head_argmax(self.lm_head, last, norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"], ws=st["lm_ws"],
                                logits=st.get("logits"))
+        if sample:      # the first token is drawn by the same two launches as every later one, at step 0
+            ops.lm_head_argmax(self.lm_head, last, norm_w=self.norm, eps=c.eps, out_ids=st["sample"]["lm_ids"], ws=st["lm_ws"],
+                               logits=st["logits"])
+            self._sample_step(st)
+        if processed:
+            ops.token_bitmap_set(st["next_ids"].view(B, 1), st["seen"], c.vocab)
         if output_hidden_states:
             step0[-1] = ops.rmsnorm(h, self.norm, c.eps).view(B, S, -1)
             hidden_steps.append(tuple(step0))
@@ -900,10 +1031,11 @@ class LlamaEngine:
         if src == cache_set:
             return hd
         B, S = hd.B, hd.S
-        processed = len(hd.skey) > 4
-        skey = self._state_key(B, hd.output_hidden_states, hd.return_logits, cache_set, processed)
+        processed, sample = hd.skey[4:5] == (True,), hd.skey[-1] == "sample"
+        skey = self._state_key(B, hd.output_hidden_states, hd.return_logits, cache_set, processed, None, sample)
         if skey not in self._graphs:
-            self._graphs[skey] = [self._make_state(B, hd.output_hidden_states, hd.return_logits, cache_set, processed), None]
+            self._graphs[skey] = [self._make_state(B, hd.output_hidden_states, hd.return_logits or sample, cache_set, processed, None,
+                                                   sample), None]
         dst, st = self._graphs[skey][0], hd.st
         (ks, vs), (kd, vd) = self._kv(src), self._kv(cache_set)
         kd[:, :B, :, :S + 1].copy_(ks[:, :B, :, :S + 1])
@@ -914,6 +1046,9 @@ class LlamaEngine:
         for k in ("logits", "hidden_buf"):
             if k in st:
                 dst[k].copy_(st[k])
+        if sample:
+            for k in ("temperature", "top_p", "top_k", "seed", "row0"):
+                dst["sample"][k].copy_(st["sample"][k])
         nd = _PrefillHandle(**hd.__dict__)
         nd.st, nd.skey, nd.tokens = dst, skey, dst["hist"][:, :hd.max_new_tokens]
         return nd
@@ -953,7 +1088,7 @@ class LlamaEngine:
             for k, v in snap.items():
                 st[k].copy_(v)
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with capture_graph(graph):
                 self._decode_step(st)
             for k, v in snap.items():   # capture does not execute; restore is a no-op safety net
                 st[k].copy_(v)
@@ -1041,7 +1176,7 @@ class LlamaEngine:
                     # That eager step was a real one and loaded the kernels; the following ones replay its capture. (A warm-up step
                     # that is rolled back, as on the greedy path, would have to undo the reorder of the KV rows as well.)
                     graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
+                    with capture_graph(graph):
                         self._decode_step(st)
                     self._graphs[skey][1] = graph
             if return_logits:
@@ -1071,7 +1206,7 @@ class LlamaEngine:
                 input_ids=None if input_ids is None else input_ids[sl],
                 inputs_embeds=None if inputs_embeds is None else inputs_embeds[sl],
                 attention_mask=None if attention_mask is None else attention_mask[sl],
-                position_ids=None if position_ids is None else position_ids[:, sl], return_dict_in_generate=True, **kw))
+                position_ids=None if position_ids is None else position_ids[:, sl], return_dict_in_generate=True, _row0=b0, **kw))
         eos = _id_list(kw.get("eos_token_id"))
         pad = kw.get("pad_token_id")
         pad = pad if pad is not None else (eos[0] if eos else 0)

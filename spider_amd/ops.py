@@ -499,6 +499,64 @@ def kv_row_gather(k_cache, v_cache, k_tmp, v_tmp, src_beam, kv_beg, kv_end, K):
               K, R, L, RA, n_kv, T, d, _stream())
 
 
+SAMPLE_MAX_K = 64       # top_k limit of the sampling kernels (sample.hip) = stride of their candidate lists
+
+
+def sample_state(rows: int, V: int, device) -> dict:
+    """Parameters, workspace and outputs of sample_partial / sample_select for `rows` rows. The parameters (temperature, top_p
+    float [1]; top_k, row0 int [1]; seed int32 [2] = the uint32 words (low, high)) are read by the kernels when they run."""
+    ns = beam_nslices(V)
+    f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
+    return dict(temperature=f32(1).fill_(1.0), top_p=f32(1).fill_(1.0), top_k=i32(1).fill_(1), seed=i32(2), row0=i32(1),
+                ws_val=f32(rows, ns, SAMPLE_MAX_K), ws_tok=i32(rows, ns, SAMPLE_MAX_K), cand_tok=i32(rows, SAMPLE_MAX_K),
+                cand_p=f32(rows, SAMPLE_MAX_K), n_keep=i32(rows), u=f32(rows))
+
+
+def sample_set_params(sm: dict, temperature: float, top_k: int, top_p: float, seed: int, row0: int = 0):
+    """this request's values into the state's parameter buffers (stream-ordered copies)"""
+    if not (1 <= int(top_k) <= SAMPLE_MAX_K):
+        raise ValueError(f"top_k has to be in [1, {SAMPLE_MAX_K}], but is {top_k}")
+    sm["temperature"].fill_(float(temperature))
+    sm["top_p"].fill_(float(top_p))
+    sm["top_k"].fill_(int(top_k))
+    sm["row0"].fill_(int(row0))
+    words = [(int(seed) >> s) & 0xFFFFFFFF for s in (0, 32)]
+    sm["seed"].copy_(torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=torch.int32))
+
+
+def sample_partial(logits, sm: dict, proc: Optional[dict] = None):
+    """Per row of raw bf16 logits [rows, V] and slice of 4096 tokens: the slice's top_k best (value, token) of the PROCESSED logits
+    (proc = the buffers of lm_head_argmax_proc; None: the raw logits) into sm['ws_val'] / sm['ws_tok']."""
+    _chk(logits, BF16, "logits")
+    rows, V = logits.shape
+    ns = beam_nslices(V)
+    _chk(sm["ws_val"], torch.float32, "ws_val"); _chk(sm["ws_tok"], torch.int32, "ws_tok"); _chk(sm["top_k"], torch.int32, "top_k")
+    assert sm["ws_val"].numel() == rows * ns * SAMPLE_MAX_K and sm["ws_tok"].numel() == rows * ns * SAMPLE_MAX_K
+    pargs = _proc_args(proc, rows, V) if proc is not None else (None,) * 7
+    _lib.call("spider_sample_partial_bf16", _p(logits), *pargs, _p(sm["top_k"]), _p(sm["ws_val"]), _p(sm["ws_tok"]), rows, V, ns,
+              _stream())
+
+
+def sample_select(sm: dict, n_hist, next_ids, V: int):
+    """One draw per row from sample_partial's workspace (csrc/sample.hip, `sample_token_host` of llm.py is its host restatement):
+    next_ids [rows]; sm['cand_tok'] / sm['cand_p'] [rows, 64] = the ranked candidates and their unnormalised probabilities,
+    sm['n_keep'] [rows] = the size of the nucleus, sm['u'] [rows] = the uniform of (seed, row0 + row, n_hist[row])."""
+    _chk(n_hist, torch.int32, "n_hist"); _chk(next_ids, torch.int32, "next_ids")
+    rows = next_ids.numel()
+    ns = beam_nslices(V)
+    for k, dt, n in (("temperature", torch.float32, 1), ("top_p", torch.float32, 1), ("top_k", torch.int32, 1), ("seed", torch.int32, 2),
+                     ("row0", torch.int32, 1), ("ws_val", torch.float32, rows * ns * SAMPLE_MAX_K),
+                     ("ws_tok", torch.int32, rows * ns * SAMPLE_MAX_K), ("cand_tok", torch.int32, rows * SAMPLE_MAX_K),
+                     ("cand_p", torch.float32, rows * SAMPLE_MAX_K), ("n_keep", torch.int32, rows), ("u", torch.float32, rows)):
+        _chk(sm[k], dt, k)
+        assert sm[k].numel() == n, f"{k}: expected {n} entries"
+    assert n_hist.numel() == rows
+    _lib.call("spider_sample_select_f32", _p(sm["ws_val"]), _p(sm["ws_tok"]), _p(sm["temperature"]), _p(sm["top_p"]), _p(sm["top_k"]),
+              _p(sm["seed"]), _p(sm["row0"]), _p(n_hist), _p(next_ids), _p(sm["cand_tok"]), _p(sm["cand_p"]), _p(sm["n_keep"]),
+              _p(sm["u"]), rows, V, ns, _stream())
+
+
 def rope_kv_append(qkv, pos, slot, cos_sin, q_out, k_cache, v_cache, B, S, n_q, n_kv, d, mrope_section=None):
     """pos [B*S] int32, or [3, B*S] with mrope_section=(t, h, w) rotary pairs per component (Qwen2.5-Omni: 16, 24, 24)."""
     _chk(qkv, BF16, "qkv"); _chk(pos, torch.int32, "pos"); _chk(slot, torch.int32, "slot")

@@ -29,6 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .graphs import capture as capture_graph
 
 BF16 = torch.bfloat16
 
@@ -139,7 +140,7 @@ def _capture(device, ent: dict, fn) -> None:
         fn()
     torch.cuda.current_stream(device).wait_stream(s)
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+    with capture_graph(g):
         ent["out"] = fn()
     ent["graph"] = g
 
@@ -649,7 +650,8 @@ class QwenOmniThinker:
         """Returns [B, S + new] token ids like GenerationMixin.generate with input_ids. Length and EOS default to the
         checkpoint's generation config as in the reference's bare `model.generate(**inputs, spk=..., use_audio_in_video=True)`
         (qwen2.5omni_spider_web.py:468): finished rows are pad-filled, the call ends when every row has emitted EOS.
-        = `prefill_begin` + `decode_finish` back to back."""
+        = `prefill_begin` + `decode_finish` back to back. do_sample / temperature / top_k / top_p / seed and the logits-processor
+        keywords go to LlamaEngine.prefill_begin as given."""
         return self.decode_finish(self.prefill_begin(input_ids, attention_mask, max_new_tokens, thinker_max_new_tokens, **kw))
 
     @torch.no_grad()
@@ -694,7 +696,9 @@ class QwenOmniThinker:
             return False
         # logits-processor keywords select the processed decode graph (LlamaEngine.prefill_begin); min_length alone does so only when
         # it exceeds the spliced prompt length, which is not known here: then either graph missing counts
-        wc = lambda processed: self.llm.would_capture(B, output_hidden_states, return_logits, cache_set, processed=processed)
+        # do_sample selects the sampling graph (temperature / top_k / top_p / seed are values the one graph reads)
+        wc = lambda processed: self.llm.would_capture(B, output_hidden_states, return_logits, cache_set, processed=processed,
+                                                      do_sample=bool(kw.get("do_sample")))
         if kw.get("repetition_penalty") not in (None, 1, 1.0) or kw.get("suppress_tokens") or kw.get("bad_words_ids") \
                 or kw.get("min_new_tokens"):
             return wc(True)

@@ -52,7 +52,8 @@ class SpiderFreeInfer:
                  story_pipe=None, story_kwargs: Optional[dict] = None, mask_box_inputs=None):
         """thinker: QwenOmniThinker (`model` of the reference); processor: the checkpoint's Qwen2_5OmniProcessor or an object with its
         three methods (apply_chat_template / __call__ / batch_decode); decoder_infer: SpiderDecoderInfer (built from `cfg` when
-        omitted); generate_kwargs: extra arguments of every `thinker.generate` call (the reference passes spk / use_audio_in_video);
+        omitted); generate_kwargs: extra arguments of every `thinker.generate` call (the reference passes spk / use_audio_in_video; do_sample /
+        temperature / top_k / top_p / seed and the logits-processor keywords reach LlamaEngine.prefill_begin as given);
         process_mm_info: the `qwen_omni_utils.process_mm_info` callable (messages, use_audio_in_video) -> (audios, images, videos);
         text-only messages need none. pipelined: `__call__` returns an EARLIER request's result (see `submit`). depth: requests in
         flight under `submit` -- 2 (default): [LLM pass of k+1 | decoder pass of k]; 3: [decode loop of k+1 | decoder pass of k, then the

@@ -193,7 +193,7 @@ class TrainedSpider:
 
     @torch.no_grad()
     def generate(self, samples, answers, predictions, predictions_text, stop_words_ids=None, num_beams=1, min_length=1,
-                 top_p=0.9, repetition_penalty=1, length_penalty=1, temperature=1, do_sample=False):
+                 top_p=0.9, repetition_penalty=1, length_penalty=1, temperature=1, do_sample=False, top_k=None, seed=None):
         inputs_embeds, attention_mask = self.prepare_generation_embedding(samples)
         end_ids = self._ids("[END]")
         stopping = [StoppingCriteriaSub(stops=[[2], end_ids[0].tolist()])]     # EOS id 2 or `[END]` (spider.py:1485-1489)
@@ -201,5 +201,6 @@ class TrainedSpider:
                                             max_new_tokens=self.max_context_len, num_beams=num_beams, do_sample=do_sample,
                                             use_cache=True, stopping_criteria=stopping, output_hidden_states=True,
                                             return_dict_in_generate=True, output_attentions=True,
-                                            repetition_penalty=repetition_penalty, min_length=min_length)
+                                            repetition_penalty=repetition_penalty, min_length=min_length, top_p=top_p,
+                                            temperature=temperature, top_k=top_k, seed=seed)
         return self.decode_outputs(samples, outputs, answers, predictions, predictions_text)

@@ -22,6 +22,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import torch
 
 from . import ops
+from .graphs import capture as capture_graph
 
 BF16 = torch.bfloat16
 
@@ -664,7 +665,7 @@ class UNetEngine:
                 self._forward(self._x_static)       # warm-up outside capture
             torch.cuda.current_stream(self.device).wait_stream(s)
             self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
+            with capture_graph(self._graph):
                 self._out_static = self._forward(self._x_static)
             self._graph_key = key
         self._x_static.copy_(x)
