@@ -96,6 +96,11 @@ WTILED_MAX_M = int(_os.environ.get("SPIDER_WTILED_MAX_M", "512"))
 
 
 def mark_weight(t: torch.Tensor) -> torch.Tensor:
+    """Mark a long-lived weight: calls may then run on layout copies of it (tile-major `_tiled`, fragment-major `_wsfm`), built on
+    first use and rebuilt when the tag (`t._version`, `t.data_ptr()`) changes. That tag sees only in-place operations on the tensor
+    itself (`t.mul_()`, `t.copy_()`) and a new storage (`t.data = ...`). A write through a view that torch does not version --
+    `t.data.mul_()`, a raw pointer -- leaves `_version` and `data_ptr()` as they were and is NOT tracked: the
+    copy stays stale. No engine writes its weights that way; code that must should drop `t._spider_tiled` / `t._spider_fm` itself."""
     t._spider_weight = True
     return t
 
