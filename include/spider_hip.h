@@ -81,6 +81,20 @@ int spider_decode_advance_seen_i32(const int* next_ids, int* cur_ids, int* pos, 
 /* bitmap [B, ceil(V/32)] |= the bits of ids [B, n] (int32); ids outside [0, V) are ignored, duplicates are harmless */
 int spider_token_bitmap_set_i32(const int* ids, void* bitmap, int B, int n, int V, void* stream);
 
+/* no_repeat_ngram_size (transformers NoRepeatNGramLogitsProcessor) as a per-step ban bitmap for the *_proc lm_head forms and the
+ * sampling step. Row b's sequence is s = prompt_ids[b, :n_prompt[0]] ++ hist[b, :n_hist[b]] (length L; prompt_ids [B, pcap],
+ * hist [B, cap], n_prompt int32 [1]: the prompt length of an input_ids call, 0 for inputs_embeds), n = ngram[0]:
+ *   ban_step[b] = ban[b] | { s[i + n - 1] : 0 <= i < L - n + 1, s[i .. i+n-1) == s[L-n+1 .. L) }     (n = 1: every token of s)
+ * n <= 0 or n > L + 1 adds nothing; ids outside [0, V) set no bit. ban / ban_step: uint32 [B, ceil(V/32)], two buffers, at most
+ * 64 KB per row. ngram int32 [1] is read when the kernel runs (one captured graph serves every size). One block per row.
+ * spider_decode_advance_seen_ngram_i32 = spider_decode_advance_seen_i32 followed by spider_ngram_ban_i32 on the advanced state
+ * (the bitmap of the NEXT step), in one launch; hist and n_hist are required. */
+int spider_ngram_ban_i32(const int* prompt_ids, const int* n_prompt, int pcap, const int* hist, const int* n_hist, int cap,
+                         const int* ngram, const void* ban, void* ban_step, int V, int B, void* stream);
+int spider_decode_advance_seen_ngram_i32(const int* next_ids, int* cur_ids, int* pos, int* slot, int* kv_end, int* hist,
+                                         int* n_hist, void* seen, const int* prompt_ids, const int* n_prompt, int pcap,
+                                         const int* ngram, const void* ban, void* ban_step, int V, int cap, int B, void* stream);
+
 /* Beam search step (transformers GenerationMixin._beam_search: _get_top_k_continuations, _get_running_beams_for_next_iteration and
  * the cache reorder; num_beams / length_penalty reach it from spider.py:1471-1508 and conversation.py:151-173). rows = B * K.
  * spider_beam_partial_bf16: per row of raw bf16 logits [rows, V] and slice of 4096 tokens (nslice = ceil(V / 4096)): ws_ms

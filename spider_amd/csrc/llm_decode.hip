@@ -725,6 +725,74 @@ __global__ void decode_advance_seen_kernel(const int* __restrict__ next_ids, int
     }
 }
 
+// no_repeat_ngram_size (transformers NoRepeatNGramLogitsProcessor), one block per row: ban_step[b] = ban[b] | { s[i + n - 1] :
+// s[i .. i+n-1) == s[L-n+1 .. L), 0 <= i < L - n + 1 } over the row's logical sequence s = prompt_ids[b, :n_prompt] ++
+// hist[b, :n_hist[b]] of length L; n = ngram[0] is read here, so one captured graph serves every size (n <= 0: ban_step = ban).
+// The static ban words are staged in LDS, every thread strides over the start positions i and ORs the bit of the token behind a
+// matching (n-1)-gram into LDS (ds_or, no return value waited for); two barriers: staged -> scanned -> stored. Nothing global is
+// written but the row's own ban_step words and, in the ADVANCE form, the row's cursors by thread 0.
+// ADVANCE: decode_advance_seen for row b by thread 0, and the scan runs for the NEXT step: the token just chosen is the last
+// element of the sequence. It stays in a register (`last`): hist[b, n_hist[b]] is written here and not read back.
+// History slots at or past `cap` were never stored; they read as -1.
+constexpr int NGRAM_THREADS = 1024;     // 4096 generated tokens + a 1.5k prompt: at most 6 start positions per thread
+template <bool ADVANCE>
+__global__ __launch_bounds__(NGRAM_THREADS) void ngram_ban_kernel(
+    const int* __restrict__ prompt_ids, const int* __restrict__ n_prompt, int pcap, int* __restrict__ hist,
+    int* __restrict__ n_hist, int cap, const int* __restrict__ ngram, const uint32_t* __restrict__ ban,
+    uint32_t* __restrict__ ban_step, int V, const int* __restrict__ next_ids, int* __restrict__ cur_ids, int* __restrict__ pos,
+    int* __restrict__ slot, int* __restrict__ kv_end, uint32_t* __restrict__ seen) {
+    extern __shared__ uint32_t ng_bits[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int W = (V + 31) / 32;
+    const int n = ngram[0];
+    int P = n_prompt[0];
+    P = P < 0 ? 0 : (P > pcap ? pcap : P);
+    const int nh_old = n_hist[b];       // read by every thread before thread 0 moves the counter (behind the first barrier)
+    const int last = ADVANCE ? next_ids[b] : 0;
+    const int nh = ADVANCE ? nh_old + 1 : nh_old;
+    const int L = P + (nh < 0 ? 0 : nh);
+    const int* prow = prompt_ids + (size_t)b * pcap;
+    const int* hrow = hist + (size_t)b * cap;
+    for (int w = tid; w < W; w += NGRAM_THREADS) ng_bits[w] = ban[(size_t)b * W + w];
+    __syncthreads();
+    if (ADVANCE && tid == 0) {
+        cur_ids[b] = last;
+        pos[b] += 1;
+        slot[b] += 1;
+        kv_end[b] += 1;
+        if (nh_old >= 0 && nh_old < cap) hist[(size_t)b * cap + nh_old] = last;
+        n_hist[b] = nh_old + 1;
+        if (last >= 0 && last < V) {
+            const size_t w = (size_t)b * W + (last >> 5);
+            seen[w] = seen[w] | (1u << (last & 31));
+        }
+    }
+    auto tok = [&](int k) -> int {      // element k < L of the logical sequence
+        if (ADVANCE && k == L - 1) return last;
+        if (k < P) return prow[k];
+        const int j = k - P;
+        return j < cap ? hrow[j] : -1;
+    };
+    if (n >= 1) {
+        const int m = n - 1;            // length of the (n-1)-gram in front of the banned token
+        const int t0 = L - m;           // where the sequence's tail starts; start positions are 0 <= i < t0
+        const int first = (m > 0 && t0 > 0) ? tok(t0) : 0;
+        for (int i = tid; i < t0; i += NGRAM_THREADS) {
+            bool eq = true;
+            if (m > 0) {
+                eq = tok(i) == first;
+                for (int j = 1; eq && j < m; ++j) eq = tok(i + j) == tok(t0 + j);
+            }
+            if (eq) {
+                const int x = tok(i + m);
+                if (x >= 0 && x < V) atomicOr(&ng_bits[x >> 5], 1u << (x & 31));
+            }
+        }
+    }
+    __syncthreads();
+    for (int w = tid; w < W; w += NGRAM_THREADS) ban_step[(size_t)b * W + w] = ng_bits[w];
+}
+
 // bitmap[b, id / 32] |= 1 << (id % 32) for every id of ids [B, n] that lies in [0, V); duplicates are harmless (atomicOr)
 __global__ __launch_bounds__(256) void token_bitmap_set_kernel(const int* __restrict__ ids, uint32_t* __restrict__ bitmap,
                                                                int B, int n, int V) {
@@ -1732,6 +1800,40 @@ int spider_decode_advance_seen_i32(const int* next_ids, int* cur_ids, int* pos, 
     SPIDER_CHECK(seen && V > 0, "decode_advance_seen: bitmap and vocabulary size required");
     decode_advance_seen_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(next_ids, cur_ids, pos, slot, kv_end, hist, n_hist,
                                                                             (uint32_t*)seen, V, cap, B);
+    SPIDER_LAUNCH_OK();
+    return 0;
+}
+
+static int ngram_args_ok(const int* prompt_ids, const int* n_prompt, int pcap, const int* hist, const int* n_hist, int cap,
+                         const int* ngram, const void* ban, const void* ban_step, int V, int B) {
+    SPIDER_CHECK(prompt_ids && n_prompt && pcap > 0 && hist && n_hist && cap > 0 && ngram,
+                 "ngram_ban: prompt_ids [B, pcap], n_prompt, hist [B, cap], n_hist and ngram are required");
+    SPIDER_CHECK(ban && ban_step && ban != ban_step && B > 0, "ngram_ban: ban and ban_step (two buffers) and B > 0 required");
+    SPIDER_CHECK(V > 0 && (size_t)((V + 31) / 32) * 4 <= 64 * 1024, "ngram_ban: the row's bitmap has to fit 64 KB of LDS");
+    return 0;
+}
+
+// ban_step [B, ceil(V/32)] = ban | the tokens that would complete an n-gram (n = ngram[0]) already in
+// prompt_ids[b, :n_prompt[0]] ++ hist[b, :n_hist[b]]
+int spider_ngram_ban_i32(const int* prompt_ids, const int* n_prompt, int pcap, const int* hist, const int* n_hist, int cap,
+                         const int* ngram, const void* ban, void* ban_step, int V, int B, void* stream) {
+    if (ngram_args_ok(prompt_ids, n_prompt, pcap, hist, n_hist, cap, ngram, ban, ban_step, V, B)) return -1;
+    ngram_ban_kernel<false><<<B, NGRAM_THREADS, (size_t)((V + 31) / 32) * 4, (hipStream_t)stream>>>(
+        prompt_ids, n_prompt, pcap, (int*)hist, (int*)n_hist, cap, ngram, (const uint32_t*)ban, (uint32_t*)ban_step, V, nullptr,
+        nullptr, nullptr, nullptr, nullptr, nullptr);
+    SPIDER_LAUNCH_OK();
+    return 0;
+}
+
+// spider_decode_advance_seen_i32, then spider_ngram_ban_i32 on the advanced state, in one launch
+int spider_decode_advance_seen_ngram_i32(const int* next_ids, int* cur_ids, int* pos, int* slot, int* kv_end, int* hist,
+                                         int* n_hist, void* seen, const int* prompt_ids, const int* n_prompt, int pcap,
+                                         const int* ngram, const void* ban, void* ban_step, int V, int cap, int B, void* stream) {
+    SPIDER_CHECK(next_ids && cur_ids && pos && slot && kv_end && seen, "decode_advance_seen_ngram: cursors and seen required");
+    if (ngram_args_ok(prompt_ids, n_prompt, pcap, hist, n_hist, cap, ngram, ban, ban_step, V, B)) return -1;
+    ngram_ban_kernel<true><<<B, NGRAM_THREADS, (size_t)((V + 31) / 32) * 4, (hipStream_t)stream>>>(
+        prompt_ids, n_prompt, pcap, hist, n_hist, cap, ngram, (const uint32_t*)ban, (uint32_t*)ban_step, V, next_ids, cur_ids, pos,
+        slot, kv_end, (uint32_t*)seen);
     SPIDER_LAUNCH_OK();
     return 0;
 }

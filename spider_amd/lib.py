@@ -38,6 +38,8 @@ SIGNATURES = {
     "spider_lm_head_argmax_proc_bf16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 11 + [_i, _i, _i, _vp]),
     "spider_decode_advance_seen_i32": (_i, [_vp] * 8 + [_i, _i, _i, _vp]),
     "spider_token_bitmap_set_i32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "spider_ngram_ban_i32": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "spider_decode_advance_seen_ngram_i32": (_i, [_vp] * 10 + [_i] + [_vp] * 3 + [_i] * 3 + [_vp]),
     "spider_beam_partial_bf16": (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
     "spider_beam_select_f32": (_i, [_vp] * 10 + [_i, _vp, _vp] + [_i] * 5 + [_vp]),
     "spider_kv_row_gather_bf16": (_i, [_vp] * 7 + [_i] * 7 + [_vp]),

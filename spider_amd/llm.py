@@ -174,15 +174,46 @@ def resolve_logits_processors(prompt_len: int, eos: Optional[List[int]], repetit
     return p, min_new, sorted(ban)
 
 
+def resolve_no_repeat_ngram(no_repeat_ngram_size) -> int:
+    """`no_repeat_ngram_size` of transformers' `generate`: None and 0 build no processor (returns 0); anything else has to be what
+    NoRepeatNGramLogitsProcessor insists on, a strictly positive integer. No upper limit: a size longer than the sequence bans
+    nothing."""
+    if no_repeat_ngram_size is None or (no_repeat_ngram_size == 0 and not isinstance(no_repeat_ngram_size, (bool, float))):
+        return 0
+    if isinstance(no_repeat_ngram_size, bool) or not isinstance(no_repeat_ngram_size, int) or no_repeat_ngram_size < 1:
+        raise ValueError(f"`no_repeat_ngram_size` has to be a strictly positive integer, but is {no_repeat_ngram_size}")
+    if no_repeat_ngram_size > 2 ** 31 - 1:
+        raise ValueError(f"`no_repeat_ngram_size` has to fit 32 bits, but is {no_repeat_ngram_size}")
+    return int(no_repeat_ngram_size)
+
+
+def ngram_banned_host(seq: Sequence[int], n: int) -> set:
+    """The tokens transformers' NoRepeatNGramLogitsProcessor(n) bans behind the sequence seq = s[0..L): x is banned iff some i in
+    [0, L - n + 1) has s[i .. i+n-1) == s[L-n+1 .. L) and s[i+n-1] == x; nothing while L + 1 < n; n = 1 bans every token of s.
+    seq is the row's input_ids (pads included) followed by its generated tokens; the generated tokens alone for an inputs_embeds
+    call -- the conventions of the penalty's `seen` set (`resolve_logits_processors`)."""
+    s = [int(t) for t in seq]
+    L, n = len(s), int(n)
+    if n < 1 or L + 1 < n:
+        return set()
+    tail = s[L - n + 1:L]
+    return {s[i + n - 1] for i in range(L - n + 1) if s[i:i + n - 1] == tail}
+
+
 def process_logits_host(logits: torch.Tensor, seen: torch.Tensor, p: float, ban: Sequence[int], eos: Optional[List[int]],
-                        n_new: int, min_new: int) -> torch.Tensor:
+                        n_new: int, min_new: int, ngram_banned: Optional[Sequence[Sequence[int]]] = None) -> torch.Tensor:
     """Host restatement of the lm_head kernels' epilogue, in fp32, on raw logits [B, V]: `seen` [B, V] bool marks the ids the
     repetition penalty applies to (every id of the row's input_ids, pads included, plus the generated ids; the generated ids alone
-    for an inputs_embeds call), `n_new` = tokens generated so far. The greedy token is the lowest-index arg-max of the result."""
+    for an inputs_embeds call), `n_new` = tokens generated so far. `ngram_banned`: per row, the ids no_repeat_ngram_size bans at
+    this step (`ngram_banned_host`); None = none. The greedy token is the lowest-index arg-max of the result."""
     lv = logits.float().clone()
     if p != 1.0:
         lv = torch.where(seen, torch.where(lv < 0, lv * p, lv / p), lv)
     V = lv.shape[-1]
+    for b, row in enumerate(ngram_banned or ()):
+        for t in row:
+            if 0 <= t < V:
+                lv[b, t] = -math.inf
     for t in ban:
         if 0 <= t < V:
             lv[:, t] = -math.inf
@@ -341,8 +372,8 @@ def resolve_beam_search(B: int, num_beams, max_batch: int, vocab: int, eos: Opti
     if output_hidden_states:
         raise NotImplementedError("output_hidden_states with num_beams > 1 is not implemented")
     if processed:
-        raise NotImplementedError("repetition_penalty / min_length / min_new_tokens / suppress_tokens / bad_words_ids with "
-                                  "num_beams > 1 are not implemented: pass their neutral values")
+        raise NotImplementedError("repetition_penalty / min_length / min_new_tokens / suppress_tokens / bad_words_ids / "
+                                  "no_repeat_ngram_size with num_beams > 1 are not implemented: pass their neutral values")
     if B * num_beams > decode_rows or B * num_beams > max_batch:
         raise ValueError(f"batch {B} x num_beams {num_beams} = {B * num_beams} rows exceed the decode graph's {decode_rows} rows "
                          f"or the engine's max_batch={max_batch}")
@@ -637,24 +668,29 @@ class LlamaEngine:
 
     @staticmethod
     def _state_key(B: int, output_hidden_states: bool, return_logits: bool, cache_set: int, processed: bool = False,
-                   beam: Optional[tuple] = None, sample: bool = False) -> tuple:
+                   beam: Optional[tuple] = None, sample: bool = False, ngram: bool = False) -> tuple:
         """key of a decode state + captured graph; requests with logits processors have their own (one more element), and so have
-        beam-search requests (B = batch rows; beam = (num_beams, continuations kept per step): three more elements) and sampling
-        requests ("sample" as the last element, behind the processors' one)"""
+        beam-search requests (B = batch rows; beam = (num_beams, continuations kept per step): three more elements), sampling
+        requests ("sample", behind the processors' element) and requests with no_repeat_ngram_size ("ngram" as the last element;
+        they are processed requests)"""
         key = (int(B), bool(output_hidden_states), bool(return_logits), int(cache_set))
         if beam is not None:
             return key + ("beam", int(beam[0]), int(beam[1]))
-        key = key + (True,) if processed else key
-        return key + ("sample",) if sample else key
+        key = key + (True,) if (processed or ngram) else key
+        key = key + ("sample",) if sample else key
+        return key + ("ngram",) if ngram else key
 
     def would_capture(self, B: int, output_hidden_states: bool = False, return_logits: bool = False, cache_set: int = 0,
-                      processed: bool = False, num_beams: int = 1, n_eos: int = 0, do_sample: bool = False) -> bool:
+                      processed: bool = False, num_beams: int = 1, n_eos: int = 0, do_sample: bool = False,
+                      no_repeat_ngram: bool = False) -> bool:
         """True when the decode loop of such a request would capture its hipGraph (state missing or not captured yet).
         processed: a request with non-neutral logits processors (repetition_penalty != 1, a ban set, or EOS banned at first)
         num_beams > 1: a beam-search request of B batch rows with n_eos EOS ids (they size the continuations kept per step)
-        do_sample: a sampling request (one graph serves every temperature / top_k / top_p / seed)"""
+        do_sample: a sampling request (one graph serves every temperature / top_k / top_p / seed)
+        no_repeat_ngram: a request with no_repeat_ngram_size > 0 (one graph serves every size)"""
         beam = (num_beams, max(2, 1 + n_eos) * num_beams) if num_beams > 1 else None
-        ent = self._graphs.get(self._state_key(B, output_hidden_states, return_logits, cache_set, processed, beam, bool(do_sample)))
+        ent = self._graphs.get(self._state_key(B, output_hidden_states, return_logits, cache_set, processed, beam, bool(do_sample),
+                                               bool(no_repeat_ngram)))
         return ent is None or ent[1] is None
 
     def _vocab_changed(self):
@@ -764,7 +800,10 @@ class LlamaEngine:
         if hs is not None:  # HF reports the normed state as the last hidden state (modeling_llama3.py:619-623)
             ops.rmsnorm(h, self.norm, c.eps, out=hs[c.layers])
         # advance the device-side cursors and append the token to the on-device history (index math only, one launch)
-        if proc is not None:    # ... and the token joins the sequence's `seen` set before the next step's lm_head
+        if st.get("ngram_bufs") is not None:    # ... and the same launch scans the sequence for the next step's n-gram bans
+            ops.decode_advance_seen_ngram(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["seen"], c.vocab,
+                                          st["hist"], st["n_hist"], st["ngram_bufs"])
+        elif proc is not None:    # ... and the token joins the sequence's `seen` set before the next step's lm_head
             ops.decode_advance_seen(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["seen"], c.vocab,
                                     st["hist"], st["n_hist"])
         else:
@@ -790,9 +829,10 @@ class LlamaEngine:
             ops.decode_advance(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["hist"], st["n_hist"])
 
     _PROC_BUFS = ("seen", "ban", "penalty", "min_new", "eos_ids", "n_eos")
+    _NGRAM_BUFS = ("prompt_ids", "n_prompt", "ngram", "ban_step")
 
     def _make_state(self, B: int, want_hidden: bool, want_logits: bool, cache_set: int = 0, processed: bool = False,
-                    beam: Optional[tuple] = None, sample: bool = False) -> dict:
+                    beam: Optional[tuple] = None, sample: bool = False, ngram: bool = False) -> dict:
         c, dv = self.cfg, self.device
         nq_d = c.n_q * c.head_dim
         # one split-KV block per CU (256): measured on Qwen-7B shapes at T~1.6k: 2.93 / 2.90 / 3.14 ms per token at 32 / 64 / 96 splits
@@ -818,7 +858,11 @@ class LlamaEngine:
             st.update(seen=i32(B, W), ban=i32(B, W), penalty=torch.ones(1, dtype=torch.float32, device=dv), min_new=i32(1),
                       eos_ids=i32(MAX_EOS_IDS), n_eos=i32(1))
             st["proc"] = {k: st[k] for k in self._PROC_BUFS + ("n_hist",)}
-        if sample:      # the parameters, workspace and outputs of the two sampling launches (the logits buffer is always there)
+        if ngram:       # no_repeat_ngram_size: the row's prompt ids, the size, and the per-step ban bitmap (static bans | n-gram bans)
+            st.update(prompt_ids=i32(B, self.max_len), n_prompt=i32(1), ngram=i32(1), ban_step=i32(B, W))
+            st["proc"]["ban"] = st["ban_step"]      # what the lm_head and sampling kernels read as the ban set
+            st["ngram_bufs"] = {k: st[k] for k in self._NGRAM_BUFS + ("ban",)}
+        if sample:     # the parameters, workspace and outputs of the two sampling launches (the logits buffer is always there)
             st["sample"] = dict(ops.sample_state(B, c.vocab, dv), lm_ids=i32(B))
         if beam is not None:    # B = batch rows * K here. The trace holds max_len steps; the second KV buffer belongs to the cache set
             K, C = beam
@@ -849,7 +893,7 @@ class LlamaEngine:
                       position_ids: Optional[torch.Tensor] = None, cache_set: int = 0, repetition_penalty=1.0, min_length=0,
                       min_new_tokens=0, suppress_tokens=None, bad_words_ids=None, length_penalty=1.0, early_stopping=False,
                       num_return_sequences=1, num_beam_groups=1, constraints=None, force_words_ids=None, temperature=1.0,
-                      top_k=None, top_p=1.0, seed=None, _whole_generate=False, _row0=0, **unused):
+                      top_k=None, top_p=1.0, seed=None, no_repeat_ngram_size=None, _whole_generate=False, _row0=0, **unused):
         """First half of `generate`: the prompt pass (KV cache of `cache_set` filled, first token chosen, decode cursors set), all
         ENQUEUED on the current stream without a host sync; returns a handle for `decode_finish`. Two requests can be in flight on
         two streams when they use different cache sets (prefill of one beside the decode loop of the other: SpiderFreeInfer's
@@ -869,6 +913,14 @@ class LlamaEngine:
         logits processors of the same names (`resolve_logits_processors`), applied on the device before the arg-max. Keyword
         arguments only -- they are not read from the checkpoint's generation config. Neutral values (1.0, no EOS ban, empty ban
         set) run the unprocessed kernels and decode graph.
+        no_repeat_ngram_size=n (an int >= 1; None / 0 = off): transformers' NoRepeatNGramLogitsProcessor -- a token that would complete
+        an n-gram already in the row's sequence gets -inf (`ngram_banned_host` is the definition; the sequence is the one the penalty
+        sees: input_ids row, pads included, + generated tokens; the generated tokens alone for inputs_embeds). Greedy and
+        do_sample=True; num_beams > 1 raises. Such a request is a processed one with a state and graph of its own (one for every n):
+        the launch that closes a decode step also scans the row's history into the next step's ban bitmap. Measured on an MI355X,
+        Qwen2.5-7B shapes, context 1536, against the same processed request without the keyword (scripts/exp/ngram_cost.py, medians
+        of 3 alternated rounds of 96 replays, rounds within 1.3 us of each other): 1 row 2722.7 -> 2726.9 us per step (+4.1 us),
+        8 rows 3471.9 -> 3479.4 us (+7.6 us).
         num_beams > 1 (2..8, batch * num_beams <= DECODE_ROWS and <= max_batch): transformers' beam search with length_penalty,
         early_stopping (False / True / "never") and num_return_sequences. The beam step runs on the device inside the decode graph
         and `beam_finalize_host` replays HF's finished-hypotheses bookkeeping at the `sync_every` points. Only `generate` accepts it
@@ -883,6 +935,7 @@ class LlamaEngine:
         sync_every, the split path, the cache set or the grouping of more than 8 rows. seed=None draws the seed from torch's default
         CPU generator (torch.manual_seed makes the call reproducible). do_sample=False ignores the three warper arguments."""
         sampling = resolve_sampling(do_sample, temperature, top_k, top_p, num_return_sequences) if num_beams == 1 else None
+        ngram = resolve_no_repeat_ngram(no_repeat_ngram_size)
         if sampling is not None:
             seed = resolve_seed(seed)
         c, dv = self.cfg, self.device
@@ -904,7 +957,7 @@ class LlamaEngine:
             pen, min_new, ban = resolve_logits_processors(S_in, _id_list(eos_token_id), repetition_penalty, min_length, min_new_tokens,
                                                           suppress_tokens, bad_words_ids)
             C_keep = resolve_beam_search(B_all, num_beams, self.max_batch, c.vocab, _id_list(eos_token_id), self.DECODE_ROWS, do_sample,
-                                         stopping_criteria, output_hidden_states, pen != 1.0 or min_new > 0 or bool(ban),
+                                         stopping_criteria, output_hidden_states, pen != 1.0 or min_new > 0 or bool(ban) or ngram > 0,
                                          num_beam_groups, constraints, force_words_ids, num_return_sequences, length_penalty,
                                          early_stopping)
             beam = (num_beams, C_keep)
@@ -914,8 +967,9 @@ class LlamaEngine:
                 pad_token_id=pad_token_id, output_hidden_states=output_hidden_states, use_graph=use_graph,
                 sync_every=sync_every, return_logits=return_logits, cache_set=cache_set, repetition_penalty=repetition_penalty,
                 min_length=min_length, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
-                bad_words_ids=bad_words_ids, **(dict(do_sample=True, temperature=sampling[0], top_k=sampling[1], top_p=sampling[2],
-                                                     seed=seed) if sampling is not None else {})), return_dict_in_generate)
+                bad_words_ids=bad_words_ids, no_repeat_ngram_size=ngram,
+                **(dict(do_sample=True, temperature=sampling[0], top_k=sampling[1], top_p=sampling[2], seed=seed)
+                   if sampling is not None else {})), return_dict_in_generate)
         if embeds_only:
             h0 = inputs_embeds.to(device=dv, dtype=BF16).contiguous()
             B, S = h0.shape[0], h0.shape[1]
@@ -929,7 +983,7 @@ class LlamaEngine:
         eos_l = _id_list(eos_token_id)
         pen, min_new, ban = resolve_logits_processors(S, eos_l, repetition_penalty, min_length, min_new_tokens, suppress_tokens,
                                                       bad_words_ids)
-        processed = pen != 1.0 or min_new > 0 or bool(ban)
+        processed = pen != 1.0 or min_new > 0 or bool(ban) or ngram > 0
         am = (attention_mask.to(dv).to(torch.int32) if attention_mask is not None
               else torch.ones(B, S, dtype=torch.int32, device=dv))
         pos2d = (am.cumsum(-1) - 1).clamp(min=0).to(torch.int32).contiguous()
@@ -961,10 +1015,10 @@ class LlamaEngine:
         # decode state (static buffers + captured hipGraph) is cached per (batch, outputs): repeated generate() calls
         # replay the same graph instead of re-capturing ~200 launches
         sample = sampling is not None
-        skey = self._state_key(B, output_hidden_states, return_logits, cache_set, processed, None, sample)
+        skey = self._state_key(B, output_hidden_states, return_logits, cache_set, processed, None, sample, ngram > 0)
         if skey not in self._graphs:
             self._graphs[skey] = [self._make_state(B, output_hidden_states, return_logits or sample, cache_set, processed, None,
-                                                   sample), None]
+                                                   sample, ngram > 0), None]
         st = self._graphs[skey][0]
         st["kv_beg"].copy_(kv_beg)
         last = h.view(B, S, -1)[:, -1].contiguous()
@@ -986,6 +1040,14 @@ class LlamaEngine:
                 ops.token_bitmap_set(input_ids.to(torch.int32).contiguous(), st["seen"], c.vocab)
             if ban:
                 ops.token_bitmap_set(torch.tensor(ban, dtype=torch.int32, device=dv)[None].expand(B, -1).contiguous(), st["ban"], c.vocab)
+            if ngram > 0:
+                # the n-gram scan reads the row's input_ids (pads included, as HF's processor does; none for inputs_embeds) in front
+                # of the generated tokens; the bans of the first token come from the prompt alone (n_hist = 0)
+                st["ngram"].fill_(ngram)
+                st["n_prompt"].fill_(0 if embeds_only else S)
+                if not embeds_only:
+                    st["prompt_ids"][:, :S].copy_(input_ids)
+                ops.ngram_ban(st["ngram_bufs"], st["hist"], st["n_hist"], c.vocab)
             if not sample:
                 ops.lm_head_argmax_proc(self.lm_head, last, st["proc"], norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"],
                                         ws=st["lm_ws"], logits=st.get("logits"))
@@ -1013,6 +1075,8 @@ class LlamaEngine:
         tokens = st["hist"][:, :max_new_tokens]
         tokens[:, 0].copy_(st["next_ids"])
         st["n_hist"].fill_(1)
+        if ngram > 0:   # the bans of the first decode step; every later step's come from its predecessor's advance launch
+            ops.ngram_ban(st["ngram_bufs"], st["hist"], st["n_hist"], c.vocab)
         logits_steps = [st["logits"].clone()] if return_logits else None
         return _PrefillHandle(B=B, S=S, st=st, skey=skey, embeds_only=embeds_only, input_ids=input_ids, max_new_tokens=max_new_tokens,
                               stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
@@ -1031,16 +1095,17 @@ class LlamaEngine:
         if src == cache_set:
             return hd
         B, S = hd.B, hd.S
-        processed, sample = hd.skey[4:5] == (True,), hd.skey[-1] == "sample"
-        skey = self._state_key(B, hd.output_hidden_states, hd.return_logits, cache_set, processed, None, sample)
+        processed, sample, ngram = hd.skey[4:5] == (True,), "sample" in hd.skey[4:], "ngram" in hd.skey[4:]
+        skey = self._state_key(B, hd.output_hidden_states, hd.return_logits, cache_set, processed, None, sample, ngram)
         if skey not in self._graphs:
             self._graphs[skey] = [self._make_state(B, hd.output_hidden_states, hd.return_logits or sample, cache_set, processed, None,
-                                                   sample), None]
+                                                   sample, ngram), None]
         dst, st = self._graphs[skey][0], hd.st
         (ks, vs), (kd, vd) = self._kv(src), self._kv(cache_set)
         kd[:, :B, :, :S + 1].copy_(ks[:, :B, :, :S + 1])
         vd[:, :B, :, :S + 1].copy_(vs[:, :B, :, :S + 1])
-        for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "kv_beg", "n_hist") + (self._PROC_BUFS if processed else ()):
+        for k in (("cur_ids", "next_ids", "pos", "slot", "kv_end", "kv_beg", "n_hist") + (self._PROC_BUFS if processed else ())
+                  + (self._NGRAM_BUFS if ngram else ())):
             dst[k].copy_(st[k])
         dst["hist"][:, :1].copy_(st["hist"][:, :1])
         for k in ("logits", "hidden_buf"):
@@ -1079,7 +1144,7 @@ class LlamaEngine:
         final = check(1, 0)
         if use_graph and graph is None and final is None and max_new_tokens > 2:
             # warm the kernels outside capture, then capture one decode step; cursors live on device
-            snap = {k: st[k].clone() for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "n_hist", "seen") if k in st}
+            snap = {k: st[k].clone() for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "n_hist", "seen", "ban_step") if k in st}
             s = torch.cuda.Stream(device=dv)
             s.wait_stream(torch.cuda.current_stream(dv))
             with torch.cuda.stream(s):

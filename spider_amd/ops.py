@@ -434,6 +434,44 @@ def decode_advance_seen(next_ids, cur_ids, pos, slot, kv_end, seen, V, hist=None
               _p(seen), V, cap, B, _stream())
 
 
+def _ngram_args(ng: dict, hist, n_hist, B: int, V: int):
+    """The buffers of the n-gram ban: ng = dict(prompt_ids int32 [B, pcap], n_prompt int32 [1], ngram int32 [1], ban / ban_step
+    int32 [B, ceil(V/32)] (uint32 bit patterns, two buffers)); hist int32 [B, cap], n_hist int32 [B]."""
+    W = bitmap_words(V)
+    for k in ("prompt_ids", "n_prompt", "ngram", "ban", "ban_step"):
+        _chk(ng[k], torch.int32, k)
+    _chk(hist, torch.int32, "hist"); _chk(n_hist, torch.int32, "n_hist")
+    assert ng["prompt_ids"].dim() == 2 and ng["prompt_ids"].shape[0] == B and ng["prompt_ids"].shape[1] > 0
+    assert hist.dim() == 2 and hist.shape[0] == B and hist.shape[1] > 0 and n_hist.numel() == B
+    assert ng["n_prompt"].numel() >= 1 and ng["ngram"].numel() >= 1
+    assert ng["ban"].numel() == B * W and ng["ban_step"].numel() == B * W, f"ban / ban_step: expected [{B}, {W}] words"
+    assert ng["ban"].data_ptr() != ng["ban_step"].data_ptr(), "ban_step must not alias ban"
+
+
+def ngram_ban(ng: dict, hist, n_hist, V):
+    """no_repeat_ngram_size: ng['ban_step'] = ng['ban'] | the tokens that would complete an n-gram (n = ng['ngram'][0]) already in
+    the row's sequence prompt_ids[b, :n_prompt[0]] ++ hist[b, :n_hist[b]] (buffers: `_ngram_args`)."""
+    B = n_hist.numel()
+    _ngram_args(ng, hist, n_hist, B, V)
+    _lib.call("spider_ngram_ban_i32", _p(ng["prompt_ids"]), _p(ng["n_prompt"]), ng["prompt_ids"].shape[1], _p(hist), _p(n_hist),
+              hist.shape[1], _p(ng["ngram"]), _p(ng["ban"]), _p(ng["ban_step"]), V, B, _stream())
+    return ng["ban_step"]
+
+
+def decode_advance_seen_ngram(next_ids, cur_ids, pos, slot, kv_end, seen, V, hist, n_hist, ng: dict):
+    """decode_advance_seen and, in the same launch, ngram_ban on the advanced state: ng['ban_step'] is the ban bitmap of the next
+    step (the token just chosen is the last element of the row's sequence)."""
+    for t, n in ((next_ids, "next_ids"), (cur_ids, "cur_ids"), (pos, "pos"), (slot, "slot"), (kv_end, "kv_end"), (seen, "seen")):
+        _chk(t, torch.int32, n)
+    B = next_ids.numel()
+    assert cur_ids.numel() == B and pos.numel() == B and slot.numel() == B and kv_end.numel() == B
+    assert seen.numel() == B * bitmap_words(V)
+    _ngram_args(ng, hist, n_hist, B, V)
+    _lib.call("spider_decode_advance_seen_ngram_i32", _p(next_ids), _p(cur_ids), _p(pos), _p(slot), _p(kv_end), _p(hist), _p(n_hist),
+              _p(seen), _p(ng["prompt_ids"]), _p(ng["n_prompt"]), ng["prompt_ids"].shape[1], _p(ng["ngram"]), _p(ng["ban"]),
+              _p(ng["ban_step"]), V, hist.shape[1], B, _stream())
+
+
 def token_bitmap_set(ids, bitmap, V):
     """bitmap [B, ceil(V/32)] |= the bits of ids [B, n] (int32); ids outside [0, V) are ignored."""
     _chk(ids, torch.int32, "ids"); _chk(bitmap, torch.int32, "bitmap")

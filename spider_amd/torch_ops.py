@@ -190,5 +190,37 @@ def _(eps2, latents, guidance, c_sample, c_eps):
     return torch.empty_like(latents)
 
 
+# ------------------------------------------------------------------------------------------ decode bookkeeping (in place)
+@_op("ngram_ban_", mutates=("ban_step",))
+def ngram_ban_(prompt_ids: torch.Tensor, n_prompt: torch.Tensor, hist: torch.Tensor, n_hist: torch.Tensor, ngram: torch.Tensor,
+               ban: torch.Tensor, ban_step: torch.Tensor, vocab: int) -> None:
+    """no_repeat_ngram_size: ban_step = ban | the tokens that would complete an n-gram (n = ngram[0]) already in the row's sequence
+    prompt_ids[b, :n_prompt[0]] ++ hist[b, :n_hist[b]] (transformers NoRepeatNGramLogitsProcessor); bitmaps int32 [B, ceil(V/32)]"""
+    ops.ngram_ban(dict(prompt_ids=prompt_ids, n_prompt=n_prompt, ngram=ngram, ban=ban, ban_step=ban_step), hist, n_hist, vocab)
+
+
+@ngram_ban_.register_fake
+def _(prompt_ids, n_prompt, hist, n_hist, ngram, ban, ban_step, vocab):
+    return None
+
+
+@_op("decode_advance_seen_ngram_", mutates=("cur_ids", "pos", "slot", "kv_end", "hist", "n_hist", "seen", "ban_step"))
+def decode_advance_seen_ngram_(next_ids: torch.Tensor, cur_ids: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
+                               kv_end: torch.Tensor, hist: torch.Tensor, n_hist: torch.Tensor, seen: torch.Tensor,
+                               prompt_ids: torch.Tensor, n_prompt: torch.Tensor, ngram: torch.Tensor, ban: torch.Tensor,
+                               ban_step: torch.Tensor, vocab: int) -> None:
+    """end of a processed decode step: the chosen token becomes the next input, joins the history and the `seen` set, the cursors
+    advance, and ban_step becomes ngram_ban_ of the advanced sequence -- one launch"""
+    ops.decode_advance_seen_ngram(next_ids, cur_ids, pos, slot, kv_end, seen, vocab, hist, n_hist,
+                                  dict(prompt_ids=prompt_ids, n_prompt=n_prompt, ngram=ngram, ban=ban, ban_step=ban_step))
+
+
+@decode_advance_seen_ngram_.register_fake
+def _(next_ids, cur_ids, pos, slot, kv_end, hist, n_hist, seen, prompt_ids, n_prompt, ngram, ban, ban_step, vocab):
+    return None
+
+
+# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops above are listed apart
+DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
             "conv2d_nhwc", "attn_self", "attn_cross_kv77", "attn_consistent", "geglu", "cfg_step")
