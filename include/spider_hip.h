@@ -167,6 +167,12 @@ int spider_attn_decode_fused_bf16(const void* qkv, const int* pos, const float* 
  * block; 1: acq_rel ticket, 2: write-through partials + relaxed ticket + sc1 loads, no fence), 0 = in the separate combine launch
  * (SPIDER_ATTN_INLINE is read once, at the first call). Returns the previous setting. */
 int spider_set_attn_inline(int on);
+/* Tuning / test aid: form of the kernel behind spider_attn_decode_fused_bf16: 1 = q RoPE once per block (through LDS), cross-lane
+ * exchanges on the VALU (DPP, v_permlane16/32_swap) and 16-byte tail stores (default), 0 = the earlier form (q RoPE in every wave,
+ * ds_bpermute exchanges, 4-byte tail stores). Same arithmetic in the same order: bit-identical output, cache rows and partials.
+ * SPIDER_ATTN_XLANE is read once, at the first use. The SCHED 1 / 2 decode GEMVs use the same VALU exchanges; their old form is
+ * spider_set_gemv_sched(0). Returns the previous setting. */
+int spider_set_attn_xlane(int on);
 /* Tuning / test aid: memory schedule of the decode GEMVs (spider_gemv_bf16 / spider_gemv_swiglu_bf16, 1..8 sequences): 0 = one request
  * at a time (activation staging vector by vector, the next weight chunks requested after the previous ones are consumed), 1 = one round
  * trip per block (default: activations and the hoisted weight chunks -- the whole row where K <= 4096 -- requested together, two register

@@ -116,10 +116,96 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---- cross-lane exchanges on the VALU ----
+// __shfl_xor compiles to ds_bpermute_b32: a round trip through the LDS pipe (address VGPR, lgkmcnt wait) on the critical path of
+// every butterfly step. The forms below fetch the same partner with DPP modifiers / v_permlane*_swap and touch no LDS-pipe
+// instruction. Blocks must be one-dimensional with a multiple of 64 threads (the 16 / 32 forms read the lane from threadIdx.x).
+// DPP source lanes must be active: call under full exec, or under an exec mask that is uniform per 16-lane row.
+//
+// Partner read by lane l (row = 16 lanes, i = l & 15; checked on the host by applying the permutations to 0..63):
+//   M   instruction(s)                                   source lane                         == l ^ M
+//   1   DPP quad_perm:[1,0,3,2]                          (l & ~3) | {1,0,3,2}[l & 3]          yes
+//   2   DPP quad_perm:[2,3,0,1]                          (l & ~3) | {2,3,0,1}[l & 3]          yes
+//   4   DPP row_half_mirror, then quad_perm:[3,2,1,0]    (l ^ 7) ^ 3: two reflections         yes (7 ^ 3 = 4)
+//   8   DPP row_ror:8                                    (l & ~15) | ((i + 8) & 15)           yes (either direction)
+//   16  v_permlane16_swap(v, v): rows 0..3 of r0 hold rows 0,0,2,2 of v, those of r1 rows 1,1,3,3
+//       partner = (l & 16) ? r0 : r1                                                          yes
+//   32  v_permlane32_swap(v, v): r0 = halves 0,0 of v, r1 = halves 1,1;  partner = (l & 32) ? r0 : r1   yes
+// For 16 / 32, {r0, r1} is {own, partner} in some order in EVERY lane, so a commutative combine is r0 (op) r1 with no select.
+template <int M>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t u) {
+    static_assert(M == 1 || M == 2 || M == 4 || M == 8 || M == 16 || M == 32, "lane_xor: M must be a power of two below 64");
+    if constexpr (M == 1) {
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0xB1, 0xf, 0xf, true);    // quad_perm:[1,0,3,2]
+    } else if constexpr (M == 2) {
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x4E, 0xf, 0xf, true);    // quad_perm:[2,3,0,1]
+    } else if constexpr (M == 4) {
+        const int t = __builtin_amdgcn_update_dpp(0, (int)u, 0x141, 0xf, 0xf, true);      // row_half_mirror: i -> i ^ 7
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, t, 0x1B, 0xf, 0xf, true);         // quad_perm:[3,2,1,0]: i -> i ^ 3
+    } else if constexpr (M == 8) {
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x128, 0xf, 0xf, true);   // row_ror:8
+    } else if constexpr (M == 16) {
+        const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+        return (threadIdx.x & 16) ? r[0] : r[1];
+    } else {
+        const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+        return (threadIdx.x & 32) ? r[0] : r[1];
+    }
+}
+template <int M>
+__device__ __forceinline__ float lane_xor(float v) { return __uint_as_float(lane_xor<M>(__float_as_uint(v))); }
+template <int M>
+__device__ __forceinline__ int lane_xor(int v) { return (int)lane_xor<M>((uint32_t)v); }
+// M = 16 / 32 where only the lanes with (lane & M) == 0 need the partner (the last rounds of a reduction towards lane 0): the
+// second result of the swap as it is, no select; the other lanes get their own value back.
+template <int M>
+__device__ __forceinline__ float lane_xor_lo(float v) {
+    static_assert(M == 16 || M == 32, "lane_xor_lo: M must be 16 or 32");
+    const uint32_t u = __float_as_uint(v);
+    if constexpr (M == 16) return __uint_as_float(__builtin_amdgcn_permlane16_swap(u, u, false, false)[1]);
+    else return __uint_as_float(__builtin_amdgcn_permlane32_swap(u, u, false, false)[1]);
+}
+// v + partner / max(v, partner): the same two operands as `v + __shfl_xor(v, M)`, and IEEE add / max are commutative, so the
+// result is bit-identical to the shuffle form in every lane
+template <int M>
+__device__ __forceinline__ float xor_add(float v) {
+    if constexpr (M == 16) {
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    } else if constexpr (M == 32) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    } else {
+        return v + lane_xor<M>(v);
+    }
+}
+template <int M>
+__device__ __forceinline__ float xor_max(float v) {
+    if constexpr (M == 16) {
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    } else if constexpr (M == 32) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    } else {
+        return fmaxf(v, lane_xor<M>(v));
+    }
+}
+// 64-lane sum / max in the order of wave_sum / wave_max (xor 32, 16, 8, 4, 2, 1): bit-identical to them. Full exec only.
+__device__ __forceinline__ float wave_sum_valu(float v) {
+    return xor_add<1>(xor_add<2>(xor_add<4>(xor_add<8>(xor_add<16>(xor_add<32>(v))))));
+}
+__device__ __forceinline__ float wave_max_valu(float v) {
+    return xor_max<1>(xor_max<2>(xor_max<4>(xor_max<8>(xor_max<16>(xor_max<32>(v))))));
+}
+// sum over the 16 lanes of a row in the order xor 1, 2, 4, 8 (the decode attention's score reduction)
+__device__ __forceinline__ float row16_sum_valu(float v) { return xor_add<8>(xor_add<4>(xor_add<2>(xor_add<1>(v)))); }
+
 // Block-wide sum for blocks of NW waves; `red` is >= NW floats of LDS. All threads get the result.
-template <int NW>
+// VALU: the wave sums through wave_sum_valu (same order, same bits) instead of six ds_bpermute round trips.
+template <int NW, bool VALU = false>
 __device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
+    v = VALU ? wave_sum_valu(v) : wave_sum(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     __syncthreads();
     if (lane == 0) red[w] = v;

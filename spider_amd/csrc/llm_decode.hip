@@ -178,6 +178,8 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16_t* __restrict__
 //   1  as 2, for rows of <= 8 chunks (K <= 4096) and NR*NB <= 2 (qkv, o): EVERY chunk of the row is requested
 //      before the prologue -- the weight stream is one round trip that overlaps the staging -- and no k loop is left.
 // spider_set_gemv_sched / SPIDER_GEMV_SCHED choose between 0 and {1, 2} (gemv_dispatch picks 1 where it applies).
+// SCHED 1 / 2 also take the RMSNorm block sum and the per-row dot reduction through wave_sum_valu (common.hpp: DPP and
+// v_permlane*_swap in wave_sum's xor order, so the same bits) where SCHED 0 keeps wave_sum's six ds_bpermute round trips.
 // ----------------------------------------------------------------------------------------------
 // 16-byte vectors a thread keeps in flight while it stages the activations (SCHED 1 / 2): one batch covers K <= 8192 (plain) or
 // 4096 (normalised: half of them are norm_w) with 4 waves per block, K <= 24576 with 8 (the down projection asks for 5)
@@ -344,7 +346,7 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
             hoist_w();
             for (int b = 0; b < NB; ++b) {
                 if (b) issue_xw(xv + (size_t)b * nv, t0);
-                const float rs = rsqrtf(block_sum<NWB>(sumsq(0.f, t0, CH), red) / (float)K + eps);
+                const float rs = rsqrtf(block_sum<NWB, true>(sumsq(0.f, t0, CH), red) / (float)K + eps);
                 norm_store(sv + (size_t)b * nv, t0, rs);
             }
         } else {
@@ -355,7 +357,7 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
                     issue_x(xv + (size_t)b * nv, i0 + t0);
                     ss = sumsq(ss, i0 + t0, CAP);
                 }
-                const float rs = rsqrtf(block_sum<NWB>(ss, red) / (float)K + eps);
+                const float rs = rsqrtf(block_sum<NWB, true>(ss, red) / (float)K + eps);
                 for (int i0 = 0; i0 < nv; i0 += CH * NT) {
                     issue_xw(xv + (size_t)b * nv, i0 + t0);
                     norm_store(sv + (size_t)b * nv, i0 + t0, rs);
@@ -496,7 +498,7 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
-        for (int r = 0; r < NR; ++r) acc[b][r] = wave_sum(acc[b][r]);
+        for (int r = 0; r < NR; ++r) acc[b][r] = SCHED ? wave_sum_valu(acc[b][r]) : wave_sum(acc[b][r]);
 
     if (lane == 0) {
 #pragma unroll
@@ -1048,7 +1050,16 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
 // ticket issues an agent-scope acquire, reduces all partials and writes the output (placement-independent
 // release/acquire hand-off; the counter is reset by the reducer, so graph replays need no memset).
 // ----------------------------------------------------------------------------------------------
-template <int D, int G, int NWV, int UR>
+//
+// XL (spider_set_attn_xlane / SPIDER_ATTN_XLANE, default on) shortens the one wave's instruction chain that is this kernel's time
+// (one wave per SIMD: nothing hides it); every product, sum, rounding and their order are those of the XL = false form, so all
+// outputs, cache rows and partials are bit-identical (tests/test_attn_xlane_gpu.py):
+//   - q RoPE once per block: lane group gi = wave * 4 + sub rotates and scales head gi (< G) into sm_q, one barrier, every lane
+//     reads its 8 dims of the G heads back. XL = false rotates all G heads in every wave (G x 16 times the work per block).
+//   - every cross-lane exchange on the VALU (lane_xor, common.hpp): DPP for the score sum over a 16-lane row (exec is uniform per
+//     row there), v_permlane16/32_swap for the merge of the four row groups, where XL = false takes a ds_bpermute round trip each
+//   - the tail stores 16 bytes per thread (one thread per head and 4 dims), as the inline-combine form does.
+template <int D, int G, int NWV, int UR, bool XL = false>
 __global__ __launch_bounds__(NWV * 64) void attn_decode_fused_kernel(
     const bf16_t* __restrict__ qkv, const int* __restrict__ pos, const float* __restrict__ cs, bf16_t* __restrict__ kc,
     bf16_t* __restrict__ vc, const int* __restrict__ kv_beg, const int* __restrict__ kv_end, float* __restrict__ part_o,
@@ -1086,9 +1097,12 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_fused_kernel(
     if (tb0 < t1) load_rows(tb0, kq, vq);
 
     const bf16_t* row = qkv + (size_t)b * (n_q + 2 * n_kv) * D;
-    const float* c = cs + (size_t)pos[b] * D;
-    float cosv[8], sinv[8];
-    {
+    // XL: only the lane groups that rotate a head (group 0 also rotates the current token's k) read the position and its table row
+    const int gi = wave * 4 + sub;
+    const bool rot = !XL || gi < G;
+    float cosv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sinv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (rot) {
+        const float* c = cs + (size_t)pos[b] * D;
         const int ci = hi_half ? dl - HALF : dl;
         const f32x4 c0 = *reinterpret_cast<const f32x4*>(c + ci), c1 = *reinterpret_cast<const f32x4*>(c + ci + 4);
         const f32x4 s0 = *reinterpret_cast<const f32x4*>(c + HALF + ci), s1 = *reinterpret_cast<const f32x4*>(c + HALF + ci + 4);
@@ -1110,11 +1124,32 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_fused_kernel(
     };
 
     float qf[G][8];
+    if constexpr (XL) {
+        // a buffer of its own: aliased with sm_o, a slow wave's read here would race with a fast wave's merge store below
+        __shared__ __attribute__((aligned(16))) float sm_q[G][D];
+        if (gi < G) {
+            float qr[8];
+            rope8(row + (size_t)(hk * G + gi) * D, qr);
+            f32x4 q0, q1;
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-        rope8(row + (size_t)(hk * G + g) * D, qf[g]);
+            for (int j = 0; j < 4; ++j) { q0[j] = qr[j] * scale; q1[j] = qr[4 + j] * scale; }
+            *reinterpret_cast<f32x4*>(&sm_q[gi][dl]) = q0;
+            *reinterpret_cast<f32x4*>(&sm_q[gi][dl + 4]) = q1;
+        }
+        __syncthreads();
 #pragma unroll
-        for (int j = 0; j < 8; ++j) qf[g][j] *= scale;
+        for (int g = 0; g < G; ++g) {
+            const f32x4 q0 = *reinterpret_cast<const f32x4*>(&sm_q[g][dl]), q1 = *reinterpret_cast<const f32x4*>(&sm_q[g][dl + 4]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { qf[g][j] = q0[j]; qf[g][4 + j] = q1[j]; }
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            rope8(row + (size_t)(hk * G + g) * D, qf[g]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) qf[g][j] *= scale;
+        }
     }
     float m[G], l[G], o[G][8];
 #pragma unroll
@@ -1130,16 +1165,24 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_fused_kernel(
             float sc = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) sc += qf[g][j] * kf[j];
-            sc += __shfl_xor(sc, 1, 64);
-            sc += __shfl_xor(sc, 2, 64);
-            sc += __shfl_xor(sc, 4, 64);
-            sc += __shfl_xor(sc, 8, 64);
+            if constexpr (XL) {
+                sc = row16_sum_valu(sc);                  // exec is uniform per 16-lane row at every call: each partner is active
+            } else {
+                sc += __shfl_xor(sc, 1, 64);
+                sc += __shfl_xor(sc, 2, 64);
+                sc += __shfl_xor(sc, 4, 64);
+                sc += __shfl_xor(sc, 8, 64);
+            }
             const float mn = fmaxf(m[g], sc);
             const float alpha = __expf(m[g] - mn);
             const float pr = __expf(sc - mn);
             l[g] = l[g] * alpha + pr;
+            // o * alpha + pr * v with the product that is rounded on its own written out: left to -ffp-contract=fast the choice differs
+            // from one inlined copy of this lambda to the next (the 4-wave G = 7 kernel fused the first product for j < 2 and the second
+            // for j >= 2, which is kept), and the two forms of the kernel would differ in the last bit
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[g][j] = o[g][j] * alpha + pr * vf[j];
+            for (int j = 0; j < 8; ++j)
+                o[g][j] = j < 2 ? __builtin_fmaf(o[g][j], alpha, pr * vf[j]) : __builtin_fmaf(pr, vf[j], o[g][j] * alpha);
             m[g] = mn;
         }
     };
@@ -1187,8 +1230,41 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_fused_kernel(
 
     // merge the 4 row sub-groups of the wave, then the 4 waves via LDS
     __shared__ float sm_m[NWV][G], sm_l[NWV][G];
-    __shared__ float sm_o[NWV][G][D];
+    __shared__ __attribute__((aligned(16))) float sm_o[NWV][G][D];
     __shared__ int sm_last;
+    if constexpr (XL) {
+        // Only lanes 0..15 are stored: the xor-16 round has to be right in rows 0 and 2, the xor-32 round in row 0, which are the
+        // lanes where lane_xor_lo returns the partner. All heads are merged before the first store (G independent chains).
+        auto merge = [&](int g, auto xl) {
+            const float m2 = xl(m[g]), l2 = xl(l[g]);
+            const float mn = fmaxf(m[g], m2);
+            const float a1 = (m[g] == -INFINITY) ? 0.f : __expf(m[g] - mn);
+            const float a2 = (m2 == -INFINITY) ? 0.f : __expf(m2 - mn);
+            l[g] = __builtin_fmaf(l[g], a1, l2 * a2);        // the partner's product rounded on its own, in both forms
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float o2 = xl(o[g][j]);
+                o[g][j] = __builtin_fmaf(o[g][j], a1, o2 * a2);
+            }
+            m[g] = mn;
+        };
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            merge(g, [](float v) { return lane_xor_lo<16>(v); });
+            merge(g, [](float v) { return lane_xor_lo<32>(v); });
+        }
+        if (lane < 16) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                f32x4 o0, o1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { o0[j] = o[g][j]; o1[j] = o[g][4 + j]; }
+                *reinterpret_cast<f32x4*>(&sm_o[wave][g][dl]) = o0;
+                *reinterpret_cast<f32x4*>(&sm_o[wave][g][dl + 4]) = o1;
+                if (lane == 0) { sm_m[wave][g] = m[g]; sm_l[wave][g] = l[g]; }
+            }
+        }
+    } else {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
 #pragma unroll
@@ -1198,11 +1274,11 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_fused_kernel(
             const float mn = fmaxf(m[g], m2);
             const float a1 = (m[g] == -INFINITY) ? 0.f : __expf(m[g] - mn);
             const float a2 = (m2 == -INFINITY) ? 0.f : __expf(m2 - mn);
-            l[g] = l[g] * a1 + l2 * a2;
+            l[g] = __builtin_fmaf(l[g], a1, l2 * a2);        // as the compiler contracted it; written out for the XL form's sake
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float o2 = __shfl_xor(o[g][j], off, 64);
-                o[g][j] = o[g][j] * a1 + o2 * a2;
+                o[g][j] = __builtin_fmaf(o[g][j], a1, o2 * a2);
             }
             m[g] = mn;
         }
@@ -1211,6 +1287,7 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_fused_kernel(
             for (int j = 0; j < 8; ++j) sm_o[wave][g][dl + j] = o[g][j];
             if (lane == 0) { sm_m[wave][g] = m[g]; sm_l[wave][g] = l[g]; }
         }
+    }
     }
     __syncthreads();
     if (nsplit > 1 && inline_combine) {
@@ -1309,6 +1386,37 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_fused_kernel(
             *reinterpret_cast<u32x2*>(out + bh * D + d4) = o2;
         }
         if (threadIdx.x == 0) __hip_atomic_store(cnt + (size_t)b * n_kv + hk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    if constexpr (XL) {
+        // one thread per (head, 4 dims): the sums of the scalar tail below, element by element, behind one 16-byte store
+        for (int idx = threadIdx.x; idx < G * (D / 4); idx += NWV * 64) {
+            const int g = idx / (D / 4), d4 = (idx % (D / 4)) * 4;
+            float mm = -INFINITY;
+#pragma unroll
+            for (int w = 0; w < NWV; ++w) mm = fmaxf(mm, sm_m[w][g]);
+            float ll = 0.f;
+            f32x4 oo = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int w = 0; w < NWV; ++w) {
+                const float a = (sm_m[w][g] == -INFINITY) ? 0.f : __expf(sm_m[w][g] - mm);
+                ll += sm_l[w][g] * a;
+                const f32x4 ov = *reinterpret_cast<const f32x4*>(&sm_o[w][g][d4]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) oo[j] += ov[j] * a;
+            }
+            const int hq = hk * G + g;
+            if (nsplit == 1) {
+                u32x2 o2;
+                o2.x = pack_bf16x2(ll > 0.f ? oo[0] / ll : 0.f, ll > 0.f ? oo[1] / ll : 0.f);
+                o2.y = pack_bf16x2(ll > 0.f ? oo[2] / ll : 0.f, ll > 0.f ? oo[3] / ll : 0.f);
+                *reinterpret_cast<u32x2*>(out + ((size_t)b * n_q + hq) * D + d4) = o2;
+            } else {
+                const size_t pi = ((size_t)b * n_q + hq) * nsplit + split;
+                *reinterpret_cast<f32x4*>(part_o + pi * D + d4) = oo;
+                if (d4 == 0) *reinterpret_cast<float2*>(part_ml + pi * 2) = float2{mm, ll};
+            }
+        }
         return;
     }
     for (int idx = threadIdx.x; idx < G * D; idx += NWV * 64) {
@@ -1710,10 +1818,26 @@ static int gemv_batch(const void* W, const void* x, void* out, const void* bias,
 // split-KV combine form of the fused decode attention: -1 = not chosen yet (SPIDER_ATTN_INLINE is read once, at the first call)
 static int g_attn_inline = -1;
 
+// form of attn_decode_fused_kernel: 1 = XL (q RoPE once per block, VALU cross-lane exchanges, 16-byte tail stores; default),
+// 0 = the earlier form (-1: SPIDER_ATTN_XLANE not read yet)
+static int g_attn_xlane = -1;
+static int attn_xlane() {
+    if (g_attn_xlane < 0) { const char* e = getenv("SPIDER_ATTN_XLANE"); g_attn_xlane = e ? (atoi(e) != 0) : 1; }
+    return g_attn_xlane;
+}
+
 // ==============================================================================================
 // C ABI
 // ==============================================================================================
 extern "C" {
+
+// form of the fused decode attention kernel (attn_decode_fused_kernel XL): 1 = q RoPE once per block + VALU cross-lane exchanges
+// (default), 0 = the earlier form; returns the previous setting. Outputs, cache rows and partials are bit-identical.
+int spider_set_attn_xlane(int on) {
+    const int prev = attn_xlane();
+    g_attn_xlane = on != 0;
+    return prev;
+}
 
 // schedule of the decode GEMVs (gemv_kernel SCHED): 0 = one memory request at a time, 1 = one trip per block (default);
 // returns the previous setting. Outputs are bit-identical.
@@ -2049,7 +2173,9 @@ int spider_attn_decode_bf16(const void* q, const void* k_cache, const void* v_ca
 // wide: 8 waves x 8 rows per lane group = 256 cache rows in flight per block (splits of >= ~100 rows); narrow: 4 x 4 = 64
 #define ATTN_FUSED_LAUNCH(G_)                                                                                   \
     do {                                                                                                        \
-        if (wide) attn_decode_fused_kernel<128, G_, 8, 8><<<grid, 512, 0, (hipStream_t)stream>>>(ATTN_FUSED_ARGS); \
+        if (wide && xlane) attn_decode_fused_kernel<128, G_, 8, 8, true><<<grid, 512, 0, (hipStream_t)stream>>>(ATTN_FUSED_ARGS); \
+        else if (wide) attn_decode_fused_kernel<128, G_, 8, 8><<<grid, 512, 0, (hipStream_t)stream>>>(ATTN_FUSED_ARGS); \
+        else if (xlane) attn_decode_fused_kernel<128, G_, 4, 4, true><<<grid, 256, 0, (hipStream_t)stream>>>(ATTN_FUSED_ARGS); \
         else attn_decode_fused_kernel<128, G_, 4, 4><<<grid, 256, 0, (hipStream_t)stream>>>(ATTN_FUSED_ARGS);   \
     } while (0)
 
@@ -2070,6 +2196,7 @@ int spider_attn_decode_fused_bf16(const void* qkv, const int* pos, const float* 
     // (the environment is read once per process; spider_set_attn_inline() switches the form afterwards: tests, tuning)
     if (g_attn_inline < 0) { const char* e = getenv("SPIDER_ATTN_INLINE"); g_attn_inline = e ? (atoi(e) < 0 ? 0 : (atoi(e) > 2 ? 2 : atoi(e))) : SPIDER_ATTN_INLINE_DEFAULT; }
     const int inline_combine = g_attn_inline;
+    const bool xlane = attn_xlane() != 0;
     static const int wide_env = [] { const char* e = getenv("SPIDER_ATTN_WIDE"); return e ? atoi(e) : -1; }();
     const bool wide = wide_env >= 0 ? wide_env != 0 : (T_max / nsplit >= 96);
     switch (G) {

@@ -54,6 +54,7 @@ SIGNATURES = {
     "spider_attn_decode_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "spider_attn_decode_fused_bf16": (_i, [_vp] * 11 + [_i, _i, _i, _i, _i, _f, _i, _vp]),
     "spider_set_attn_inline": (_i, [_i]),
+    "spider_set_attn_xlane": (_i, [_i]),
     "spider_set_gemv_sched": (_i, [_i]),
     "spider_set_ws_inlaunch": (_i, [_i]),
     "spider_gemm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _l, _vp]),
