@@ -43,6 +43,45 @@ from . import ops
 from .graphs import capture as capture_graph
 
 BF16 = torch.bfloat16
+FP8 = torch.float8_e4m3fn       # OCP e4m3fn: max 448 (byte 0x7e), 1.0 = 0x38 -- the FP8 of gfx950, not MI300's e4m3fnuz
+FP8_MAX = 448.0
+WEIGHT_DTYPES = ("bf16", "fp8")
+
+
+def resolve_weight_dtype(weight_dtype) -> str:
+    """`weight_dtype` of LlamaEngine: "bf16" (default) or "fp8" (weight-only e4m3 stream for the decode GEMVs)"""
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype has to be one of {WEIGHT_DTYPES}, but is {weight_dtype!r}")
+    return weight_dtype
+
+
+def quantize_fp8_rows(W: torch.Tensor):
+    """Per-row weight-only FP8: W [N, K] -> (q [N, K] float8_e4m3fn, scale [N] float32) with
+        scale[n] = 2^ceil(log2(max|W[n, :]| / 448))   (1.0 for an all-zero row),   q[n, :] = fp8(W[n, :] / scale[n]).
+    The scale is a power of two on purpose: e4m3 has 3 mantissa bits, so W_eff = float(q) * scale is a bf16 number, and a
+    power-of-two factor commutes with every fp32 rounding. A model quantised this way IS a bf16 model with weights W_eff:
+    kernels that stream q and scale the fp32 dot product by scale[n] compute, up to summation order, what the bf16 kernels
+    compute on W_eff. The relative precision of e4m3 does not depend on the scale, so the restriction costs no accuracy.
+    Pure torch; runs wherever W lives."""
+    if W.dim() != 2:
+        raise ValueError(f"quantize_fp8_rows: expected a [N, K] matrix, got {tuple(W.shape)}")
+    Wf = W.detach().float()
+    amax = Wf.abs().amax(dim=1)
+    # no rounded logarithm or division: amax = m * 2^e with m in [0.5, 1) and 448 = 0.875 * 2^9, so amax / 448 = (m / 0.875) * 2^(e - 9)
+    # lies in (0.5, 1] * 2^(e - 9) when m <= 0.875 and in (1, 1.15) * 2^(e - 9) otherwise
+    m, e = torch.frexp(amax)
+    e = (e - 9 + (m > 0.875).to(e.dtype)).clamp(-126, 127)    # a normal fp32 power of two (rows below 448 * 2^-126 lose range)
+    scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), e), torch.ones_like(amax))
+    q = (Wf / scale[:, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+    return q, scale
+
+
+def dequantize_fp8_rows(q: torch.Tensor, scale: torch.Tensor, dtype=BF16) -> torch.Tensor:
+    """W_eff = float(q) * scale[:, None] in `dtype` (exact in bf16 for the scales of quantize_fp8_rows)"""
+    return (q.float() * scale.float()[:, None]).to(dtype)
+
+
+dequantize = dequantize_fp8_rows
 
 
 @dataclass
@@ -523,8 +562,27 @@ class LlamaEngine:
     # Measured on MI355X, Qwen2.5-7B shapes at context 1536 (scripts/exp/decode_vs_batch.py), ms per decode step by rows 1 / 2 / 3 / 4 / 5 / 8:
     # row-major GEMVs 2.84 / 3.28 / 3.75 / 4.36 (then fragment-major 3.21 / 3.43); fragment-major from 2 rows: 2.99 / 3.09 / 3.16 / 3.23 / 3.43.
     FM_MIN_BATCH = int(os.environ.get("SPIDER_DECODE_FM_MIN", "2"))
+    # weight_dtype="fp8" engines: decode graphs of up to this many rows stream the e4m3 bytes (csrc/gemv_w8.hip, which exists for 1..4
+    # rows), larger ones take the bf16 route above on the dequantised weights. Measured on MI355X, Qwen2.5-7B shapes at context 1536
+    # (scripts/exp/fp8_decode_cost.py: both engines alternated in one process, 3 rounds of 96 replays, medians; rounds within 1 us),
+    # us per captured decode step by rows 1 / 2 / 3 / 4: bf16 on the route above (row-major at 1, fragment-major from 2)
+    # 2638 / 2911 / 2996 / 3063, fp8 1823 / 2162 / 2536 / 3003 = 0.69 / 0.74 / 0.85 / 0.98 of it. 2 % at 4 rows is below the 3 % that
+    # counts as a difference, so the range stops at 3.
+    FP8_MAX_ROWS = 3
 
-    def __init__(self, cfg: LLMConfig, weights: dict, device="cuda:0", max_batch: int = 1, max_len: int = 4096):
+    def __init__(self, cfg: LLMConfig, weights: dict, device="cuda:0", max_batch: int = 1, max_len: int = 4096,
+                 weight_dtype: str = "bf16"):
+        """weight_dtype="fp8": weight-only FP8 for the decode weight stream. w_qkv, w_o, w_gu and w_down of every layer are
+        quantised per output row (`quantize_fp8_rows`: OCP e4m3 with a power-of-two scale; embeddings, lm_head, norms and biases
+        stay bf16) and the layer's bf16 matrices are REPLACED by the dequantised W_eff, which bf16 holds exactly. The engine then
+        is a bf16 model with weights W_eff in two encodings: prefill, the fragment-major copies and decode graphs of more than
+        FP8_MAX_ROWS rows run on W_eff as before, and decode steps of up to FP8_MAX_ROWS rows stream the bytes q (`*_q8`) and
+        multiply the fp32 dot product by the row's scale (`*_s8`) -- the same function up to summation order, half the bytes per
+        token. Memory: q is kept beside W_eff, about 1.5x the layer weights of a bf16 engine without fragment-major copies.
+        The default "bf16" changes nothing: no tensor, no kernel, no graph key."""
+        self.weight_dtype = resolve_weight_dtype(weight_dtype)
+        if self.weight_dtype == "fp8" and (cfg.hidden % 16 or cfg.inter % 16 or (cfg.n_q * cfg.head_dim) % 16):
+            raise ValueError("weight_dtype='fp8' needs hidden, inter and n_q * head_dim to be multiples of 16 (16 weights per 16-byte load)")
         self.cfg, self.device = cfg, torch.device(device)
         self.max_batch, self.max_len = max_batch, max_len
         dv = self.device
@@ -544,6 +602,11 @@ class LlamaEngine:
                 w_gu=torch.cat([g(p + "mlp.gate_proj.weight"), g(p + "mlp.up_proj.weight")], 0).contiguous(),
                 w_down=g(p + "mlp.down_proj.weight"),
                 ln1=g(p + "input_layernorm.weight"), ln2=g(p + "post_attention_layernorm.weight"))
+            if self.weight_dtype == "fp8":
+                for k in ("w_qkv", "w_o", "w_gu", "w_down"):
+                    q, sc = quantize_fp8_rows(lw[k])
+                    lw[k] = dequantize_fp8_rows(q, sc).contiguous()      # W_eff: what every bf16 kernel of this engine reads
+                    lw[k + "_q8"], lw[k + "_s8"] = q.contiguous(), sc.contiguous()
             self.layers.append(lw)
         # Batched decode (5..8 sequences per graph) streams a second, fragment-major copy of every decode weight (ops.repack_fm16:
         # 1 KiB contiguous per wave instruction of the skinny MFMA kernels). Memory is laid out for 288 GB of HBM: the copy
@@ -561,7 +624,7 @@ class LlamaEngine:
 
     # ------------------------------------------------------------------ construction helpers
     @classmethod
-    def random_init(cls, cfg: LLMConfig, device="cuda:0", max_batch=1, max_len=4096, seed=0, std=0.02):
+    def random_init(cls, cfg: LLMConfig, device="cuda:0", max_batch=1, max_len=4096, seed=0, std=0.02, weight_dtype="bf16"):
         """Random N(0, std^2) weights of the architecture's true shapes, created directly in HBM
         (init scheme of modeling_llama3.py:405-414). Used by bench.py: timing is weight-value independent."""
         gen = torch.Generator(device=device).manual_seed(seed)
@@ -586,19 +649,20 @@ class LlamaEngine:
             w[p + "mlp.down_proj.weight"] = r(cfg.hidden, cfg.inter)
             w[p + "input_layernorm.weight"] = one(cfg.hidden)
             w[p + "post_attention_layernorm.weight"] = one(cfg.hidden)
-        return cls(cfg, w, device, max_batch, max_len)
+        return cls(cfg, w, device, max_batch, max_len, weight_dtype=weight_dtype)
 
     @classmethod
-    def from_pretrained(cls, path: str, device="cuda:0", max_batch=1, max_len=4096):
+    def from_pretrained(cls, path: str, device="cuda:0", max_batch=1, max_len=4096, weight_dtype="bf16"):
         """Load an HF checkpoint directory: config.json + model.safetensors(.index.json + shards) or pytorch_model.bin
-        (spider_amd/checkpoint.py). From a Qwen2.5-Omni directory only `thinker.model.*` / `thinker.lm_head.*` are read."""
+        (spider_amd/checkpoint.py). From a Qwen2.5-Omni directory only `thinker.model.*` / `thinker.lm_head.*` are read.
+        weight_dtype="fp8" quantises the layer matrices at load (see the constructor)."""
         from .checkpoint import load_state_dict, read_config
 
         def keep(k: str):
             kk = k.replace("thinker.model.", "model.").replace("thinker.lm_head.", "lm_head.")
             return kk if kk.startswith(("model.", "lm_head.")) else None
         cfg = LLMConfig.from_hf_dict(read_config(path))
-        eng = cls(cfg, load_state_dict(path, keep=keep), device, max_batch, max_len)
+        eng = cls(cfg, load_state_dict(path, keep=keep), device, max_batch, max_len, weight_dtype=weight_dtype)
         eng.generation_config = read_generation_config(path)
         return eng
 
@@ -737,9 +801,16 @@ class LlamaEngine:
         if hs is not None:
             hs[0].copy_(h)
         fm = self.fm_batch and B >= self.FM_MIN_BATCH
+        # FP8 engines: up to FP8_MAX_ROWS rows the four layer GEMVs stream the e4m3 bytes (the lm_head stays on its bf16 route)
+        w8 = self.weight_dtype == "fp8" and B <= min(self.FP8_MAX_ROWS, ops.W8_MAX_ROWS)
         fuse_norm = not fm and B < 5      # the row-major GEMV folds the RMSNorm for up to 4 rows; the skinny MFMA GEMM (fm) carries it in its weights
+        w8_fuse = w8 and ops.w8_norm_fits(B, c.hidden)     # (a hidden size beyond the kernel's LDS budget: RMSNorm in its own launch)
         for l, lw in enumerate(self.layers):
-            if fuse_norm:
+            if w8 and w8_fuse:
+                ops.gemv_w8(lw["w_qkv_q8"], lw["w_qkv_s8"], h, bias=lw["b_qkv"], norm_w=lw["ln1"], eps=c.eps, out=st["qkv"])
+            elif w8:
+                ops.gemv_w8(lw["w_qkv_q8"], lw["w_qkv_s8"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), bias=lw["b_qkv"], out=st["qkv"])
+            elif fuse_norm:
                 ops.gemv(lw["w_qkv"], h, bias=lw["b_qkv"], norm_w=lw["ln1"], eps=c.eps, out=st["qkv"])
             elif fm:
                 ops.gemv_fm(lw["w_qkv_fm"], h, lw["w_qkv"].shape[0], bias=lw["b_qkv"], out=st["qkv"], norm_eps=c.eps)
@@ -753,7 +824,14 @@ class LlamaEngine:
                                    B, 1, c.n_q, c.n_kv, c.head_dim)
                 ops.attn_decode(st["q"], k_cache[l], v_cache[l], st["kv_end"], kv_beg=st["kv_beg"],
                                 nsplit=st["nsplit"], ws=st["attn_ws"], out=st["attn"])
-            if fm:
+            if w8:
+                h1 = ops.gemv_w8(lw["w_o_q8"], lw["w_o_s8"], st["attn"], res=h, out=st["h1"])
+                if w8_fuse:
+                    ops.gemv_swiglu_w8(lw["w_gu_q8"], lw["w_gu_s8"], h1, norm_w=lw["ln2"], eps=c.eps, out=st["act"])
+                else:
+                    ops.gemv_swiglu_w8(lw["w_gu_q8"], lw["w_gu_s8"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
+                h = ops.gemv_w8(lw["w_down_q8"], lw["w_down_s8"], st["act"], res=h1, out=st["h2"][l & 1])
+            elif fm:
                 h1 = ops.gemv_fm(lw["w_o_fm"], st["attn"], c.hidden, res=h, out=st["h1"])
                 ops.gemv_swiglu_fm(lw["w_gu_fm"], h1, out=st["act"], norm_eps=c.eps)
                 h = ops.gemv_fm(lw["w_down_fm"], st["act"], c.hidden, res=h1, out=st["h2"][l & 1])

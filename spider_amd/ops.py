@@ -279,6 +279,62 @@ def gemv_swiglu(W_gate_up, x, norm_w=None, eps=0.0, out=None):
     return out
 
 
+FP8 = torch.float8_e4m3fn      # OCP e4m3fn (448 = 0x7e), the FP8 of gfx950 -- not MI300's e4m3fnuz
+W8_LDS_MAX_DEFAULT = 160 * 1024 - 256  # bytes of staged activations per block (csrc/gemv_w8.hip: W8_LDS_BUDGET_BYTES)
+W8_MAX_ROWS = 4                # rows the weight-only FP8 GEMVs exist for
+W8_LDS_MAX = min(int(_os.environ.get("SPIDER_W8_LDS_MAX", "0")) or W8_LDS_MAX_DEFAULT, 160 * 1024 - 256)   # mirror of csrc/gemv_w8.hip
+
+
+def w8_norm_fits(B: int, K: int) -> bool:
+    """True when gemv_w8 / gemv_swiglu_w8 can fuse the RMSNorm for B rows of K: the staged activations (rows padded to whole
+    1024-element chunks) fit the kernel's LDS budget (csrc/gemv_w8.hip: W8_LDS_BUDGET)"""
+    return B * ((K + 1023) // 1024) * 2048 <= W8_LDS_MAX
+
+
+def _chk_w8(Wq, scale, x, name):
+    _chk(Wq, FP8, name); _chk(scale, torch.float32, "scale"); _chk(x, BF16, "x")
+    if Wq.dim() != 2 or scale.numel() != Wq.shape[0]:
+        raise ValueError(f"{name}: expected a [N, K] weight with one scale per row, got {tuple(Wq.shape)} and {scale.numel()} scales")
+    K = Wq.shape[1]
+    if x.shape[-1] != K:
+        raise ValueError(f"{name}: x[..., {x.shape[-1]}] vs {name}[{Wq.shape[0]}, {K}]")
+    return K, x.numel() // K
+
+
+def gemv_w8(Wq, scale, x, bias=None, res=None, norm_w=None, eps=0.0, out=None):
+    """`gemv` on weight-only FP8: Wq [N, K] float8_e4m3fn, scale [N] fp32 per weight row (llm.quantize_fp8_rows);
+    out[b,n] = scale[n] * sum_k xin[b,k] f32(Wq[n,k]) (+bias) (+res), the fp32 sum scaled once after the reduction. 1 <= B <= 4,
+    K % 16 == 0."""
+    K, B = _chk_w8(Wq, scale, x, "Wq")
+    N = Wq.shape[0]
+    for t, n, cnt in ((bias, "bias", N), (res, "res", B * N), (norm_w, "norm_w", K)):
+        if t is not None:
+            _chk(t, BF16, n)
+            assert t.numel() == cnt, f"{n}: expected {cnt} elements"
+    if out is None:
+        out = torch.empty(B, N, dtype=BF16, device=x.device)
+    _chk(out, BF16, "out")
+    assert out.numel() == B * N
+    _lib.call("spider_gemv_w8", _p(Wq), _p(scale), _p(x), _p(out), _p(bias), _p(res), _p(norm_w), float(eps), B, N, K, _stream())
+    return out
+
+
+def gemv_swiglu_w8(Wq_gate_up, scale, x, norm_w=None, eps=0.0, out=None):
+    """`gemv_swiglu` on weight-only FP8: Wq_gate_up [2 I, K] = [gate rows | up rows], scale [2 I]. 1 <= B <= 4, K % 16 == 0."""
+    K, B = _chk_w8(Wq_gate_up, scale, x, "Wq_gate_up")
+    I = Wq_gate_up.shape[0] // 2
+    assert Wq_gate_up.shape[0] == 2 * I
+    if norm_w is not None:
+        _chk(norm_w, BF16, "norm_w")
+        assert norm_w.numel() == K
+    if out is None:
+        out = torch.empty(B, I, dtype=BF16, device=x.device)
+    _chk(out, BF16, "out")
+    assert out.numel() == B * I
+    _lib.call("spider_gemv_swiglu_w8", _p(Wq_gate_up), _p(scale), _p(x), _p(out), _p(norm_w), float(eps), B, I, K, _stream())
+    return out
+
+
 def repack_fm16(W: torch.Tensor, norm_w: Optional[torch.Tensor] = None) -> torch.Tensor:
     """W [N, K] bf16 (K % 64 == 0); with norm_w [K] the copy holds bf16(W * norm_w) for the kernels' fold_rmsnorm form.
     W -> fragment-major copy [ceil(N/16), K/64, 2, 64, 8] for the *_fm kernels: piece (rg, kb, sx)

@@ -220,7 +220,34 @@ def _(next_ids, cur_ids, pos, slot, kv_end, hist, n_hist, seen, prompt_ids, n_pr
     return None
 
 
-# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops above are listed apart
+# ------------------------------------------------------------------------------------------ weight-only FP8 decode GEMVs
+@_op("gemv_w8")
+def gemv_w8(wq: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, bias: Optional[torch.Tensor] = None,
+            res: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6) -> torch.Tensor:
+    """nn.Linear at decode on weight-only FP8: wq [N, K] float8_e4m3fn, scale [N] fp32 per weight row; x [B <= 4, K] bf16 ->
+    [B, N] bf16 = scale[n] * (xin @ f32(wq)^T) (+bias) (+res), xin = RMSNorm(x) * norm_w when norm_w is given"""
+    return ops.gemv_w8(wq, scale, x.contiguous(), bias=bias, res=res, norm_w=norm_w, eps=eps)
+
+
+@gemv_w8.register_fake
+def _(wq, scale, x, bias=None, res=None, norm_w=None, eps=1e-6):
+    return x.new_empty(x.numel() // wq.shape[1], wq.shape[0])
+
+
+@_op("gemv_swiglu_w8")
+def gemv_swiglu_w8(wq_gate_up: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, norm_w: Optional[torch.Tensor] = None,
+                   eps: float = 1e-6) -> torch.Tensor:
+    """LlamaMLP gate / up + SiLU * mul on weight-only FP8: wq_gate_up [2 I, K] = [gate rows | up rows], scale [2 I]; -> [B <= 4, I]"""
+    return ops.gemv_swiglu_w8(wq_gate_up, scale, x.contiguous(), norm_w=norm_w, eps=eps)
+
+
+@gemv_swiglu_w8.register_fake
+def _(wq_gate_up, scale, x, norm_w=None, eps=1e-6):
+    return x.new_empty(x.numel() // wq_gate_up.shape[1], wq_gate_up.shape[0] // 2)
+
+
+# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops and the FP8 GEMVs above are listed apart
+W8_OP_NAMES = ("gemv_w8", "gemv_swiglu_w8")
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
             "conv2d_nhwc", "attn_self", "attn_cross_kv77", "attn_consistent", "geglu", "cfg_step")
