@@ -321,7 +321,8 @@ int spider_rope_rows_bf16(void* x, const float* cos_sin, long row_stride, int ro
 /* ======================= UNet elementwise / normalisation (HBM-bound) ======================= */
 
 /* GroupNorm(+SiLU) on NHWC (ResnetBlock2D.norm1/2, Transformer2DModel.norm, conv_norm_out).
- * ws: B*spider_groupnorm_nchunk(HW)*G*2 floats. */
+ * ws: B*spider_groupnorm_nchunk(HW)*G*2 floats of scratch; what the call leaves there is private (a centred (mean, M2) per chunk
+ * and group, not the public partial format below) and must not be handed to spider_groupnorm_apply_* / spider_gemm_gn_in_*. */
 int spider_groupnorm_nchunk(int HW);
 int spider_groupnorm_nhwc_bf16(const void* x, const void* gamma, const void* beta, void* y, void* ws, int B, int HW,
                                int C, int G, float eps, int silu, void* stream);
@@ -342,7 +343,11 @@ int spider_groupnorm_cat_nhwc_bf16(const void* x1, const void* x2, const void* g
  *   spider_groupnorm_stats_nhwc_*: the statistics pass alone (any nchunk).
  *   spider_groupnorm_apply_nhwc_*: normalise (+ SiLU) with given partials.
  *   spider_gemm_gn_in_*: C = GroupNorm(A) W^T + bias with the normalisation applied to A on its way into LDS (norm + proj_in in
- *       one launch); c32d optional fp32 copy of C (fp32 residual stream). */
+ *       one launch); c32d optional fp32 copy of C (fp32 residual stream).
+ * Limit of this format: every consumer takes var = Q / n - mean^2 from the fp32 sums, which loses about 2 log2(|mean| / sigma) bits
+ * of a group whose mean is large against its spread (relative error of the normalised value ~1e-6 at |mean| / sigma = 4, ~3e-4 at 64).
+ * The entry points that make their own statistics (spider_groupnorm_nhwc_*, spider_groupnorm_f32in_nhwc_* with partial == NULL)
+ * do not go through it and have no such dependence. */
 int spider_conv_nhwc_gn_bf16(const void* x, const void* w, void* y, const void* bias, const void* res, const void* rowbias,
                              int B, int Hin, int Win, int Cin, int Cout, int kh, int kw, int stride, int pad_h, int pad_w,
                              int dil, int up_h, int up_w, int act, float act_param, float out_scale, int w_tiled,

@@ -21,7 +21,14 @@ namespace {
 // C1 channels in x; the kernel reads the two sources in place and writes the concatenated tensor to `cat` on the way (the
 // shortcut conv and pass 2 read it) -- the separate concat launch and its read pass are gone.
 // X32: the input is the fp32 master of the residual stream (precise mode: no cat form)
-template <bool X32>
+// CEN: the PRIVATE centred format of the GroupNorm entry points that run both passes themselves (ws, never handed out): per chunk
+// and group (mean, M2 = sum (x - mean)^2), the chunk's count following from its geometry. A thread sums its pixels of a channel
+// relative to the first of them (a sample of what it sums, so s and q stay at the size of the spread whatever |mean| / sigma is; a
+// pivot that happens to be an outlier costs that thread alone a few bits), turns them into (mean, M2) and from there on means are
+// kept as offsets from the group's pivot -- its first channel at the chunk's first pixel -- and merged by Chan's formula in a fixed
+// order: pixel lanes, then the channels of a group; gn_apply_kernel (centered = 1) merges the chunks. No step subtracts two large
+// numbers, and the mean is rounded at its own size once per chunk. CEN = false is the public (sum, sum of squares) format, unchanged.
+template <bool X32, bool CEN = false>
 __global__ void gn_stats_kernel(const h16_t* __restrict__ x, float* __restrict__ partial, int HW, int C, int G,
                                 int nchunk, int KP, const h16_t* __restrict__ x2, int C1, h16_t* __restrict__ cat) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -32,6 +39,7 @@ __global__ void gn_stats_kernel(const h16_t* __restrict__ x, float* __restrict__
     const int v = threadIdx.x % cv, pl = threadIdx.x / cv;
     const int per = (HW + nchunk - 1) / nchunk;
     const int p0 = chunk * per, p1 = min(HW, p0 + per);
+    const int cpg = C / G;
     float s[8], q[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
@@ -39,6 +47,38 @@ __global__ void gn_stats_kernel(const h16_t* __restrict__ x, float* __restrict__
     const bool second = x2 != nullptr && v * 8 >= C1;
     const int ld = second ? C - C1 : (x2 ? C1 : C);
     const h16_t* xb = (second ? x2 + (size_t)b * HW * ld + (v * 8 - C1) : x + (size_t)b * HW * ld + v * 8);
+    // CEN: channel c at the chunk's first pixel (a trailing chunk may be empty: p0 >= HW, nothing is read)
+    auto pivot_of = [&](int c) -> float {
+        if (p0 >= p1) return 0.f;
+        if (X32) return reinterpret_cast<const float*>(x)[((size_t)b * HW + p0) * C + c];
+        if (x2 == nullptr) return h16_to_f32(x[((size_t)b * HW + p0) * C + c]);
+        return h16_to_f32(c < C1 ? x[((size_t)b * HW + p0) * C1 + c] : x2[((size_t)b * HW + p0) * (C - C1) + (c - C1)]);
+    };
+    // CEN: pixels of this chunk, and of them those pixel lane k owns (p0 + k, p0 + k + KP, ...)
+    const int np = max(p1 - p0, 0);
+    auto lane_count = [&](int k) -> int { return k < np ? (np - k + KP - 1) / KP : 0; };
+    float piv[8], pg[8];      // this thread's own first value of channel j; the pivot of that channel's group
+#pragma unroll
+    for (int j = 0; j < 8; ++j) piv[j] = pg[j] = 0.f;
+    if (CEN && pl < np) {
+        if (X32) {
+            const float* xf = reinterpret_cast<const float*>(x) + ((size_t)b * HW + p0 + pl) * C + v * 8;
+            const f32x4 f0 = *reinterpret_cast<const f32x4*>(xf), f1 = *reinterpret_cast<const f32x4*>(xf + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { piv[j] = f0[j]; piv[4 + j] = f1[j]; }
+        } else {
+            const u32x4 f = *reinterpret_cast<const u32x4*>(xb + (size_t)(p0 + pl) * ld);
+            const uint32_t fw[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { piv[2 * j] = h16lo_to_f32(fw[j]); piv[2 * j + 1] = h16hi_to_f32(fw[j]); }
+        }
+        int g = (v * 8) / cpg, r = v * 8 - g * cpg;     // group of channel v * 8 + j by a carry step, not 8 divisions
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            pg[j] = (j == 0 || r == 0) ? pivot_of(g * cpg) : pg[j > 0 ? j - 1 : 0];     // one load per group this vector touches
+            if (++r == cpg) { r = 0; ++g; }
+        }
+    }
     // 4 independent 16-byte loads in flight per thread (a runtime-trip loop with one load per iteration would
     // serialise the L2/HBM round trips)
     if (X32) {
@@ -53,9 +93,15 @@ __global__ void gn_stats_kernel(const h16_t* __restrict__ x, float* __restrict__
                 a[u][1] = ok ? *reinterpret_cast<const f32x4*>(xf + (size_t)pp * C + 4) : f32x4{0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
+            for (int u = 0; u < 4; ++u) {
+                const bool ok = px + u * KP < p1;       // (CEN: a padding zero is not a value at distance -pivot)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { const float t = a[u][j >> 2][j & 3]; s[j] += t; q[j] += t * t; }
+                for (int j = 0; j < 8; ++j) {
+                    float t = a[u][j >> 2][j & 3];
+                    if (CEN) t = ok ? t - piv[j] : 0.f;
+                    s[j] += t; q[j] += t * t;
+                }
+            }
         }
     } else
     for (int px = p0 + pl; px < p1; px += 4 * KP) {
@@ -75,12 +121,25 @@ __global__ void gn_stats_kernel(const h16_t* __restrict__ x, float* __restrict__
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const uint32_t aw[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+            const bool ok = px + u * KP < p1;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float lo = h16lo_to_f32(aw[j]), hi = h16hi_to_f32(aw[j]);
+                float lo = h16lo_to_f32(aw[j]), hi = h16hi_to_f32(aw[j]);
+                if (CEN) { lo = ok ? lo - piv[2 * j] : 0.f; hi = ok ? hi - piv[2 * j + 1] : 0.f; }
                 s[2 * j] += lo; q[2 * j] += lo * lo;
                 s[2 * j + 1] += hi; q[2 * j + 1] += hi * hi;
             }
+        }
+    }
+    if (CEN) {
+        // this thread's sums about its own first value -> (mean as an offset from the group's pivot, M2)
+        const int nt = lane_count(pl);
+        const float inv = nt > 0 ? 1.f / (float)nt : 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float dm = s[j] * inv;
+            q[j] = fmaxf(q[j] - s[j] * dm, 0.f);
+            s[j] = nt > 0 ? (piv[j] - pg[j]) + dm : 0.f;
         }
     }
     *reinterpret_cast<f32x4*>(sm_s + pl * C + v * 8) = f32x4{s[0], s[1], s[2], s[3]};
@@ -91,18 +150,47 @@ __global__ void gn_stats_kernel(const h16_t* __restrict__ x, float* __restrict__
     // channel totals over the KP pixel lanes, kept in row 0
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         float ts = 0.f, tq = 0.f;
-        for (int k = 0; k < KP; ++k) { ts += sm_s[k * C + c]; tq += sm_q[k * C + c]; }
+        if (CEN) {      // Chan: (na, ts, tq) absorbs lane k's (nb, mean, M2)
+            float na = 0.f;
+            for (int k = 0; k < KP; ++k) {
+                const float nb = (float)lane_count(k);
+                if (nb > 0.f) {
+                    const float d = sm_s[k * C + c] - ts, w = nb * __builtin_amdgcn_rcpf(na + nb);     // (a weight 1 ulp off is still a weight)
+                    ts += d * w;
+                    tq += sm_q[k * C + c] + d * d * (na * w);
+                    na += nb;
+                }
+            }
+        } else {
+            for (int k = 0; k < KP; ++k) { ts += sm_s[k * C + c]; tq += sm_q[k * C + c]; }
+        }
         sm_s[c] = ts;
         sm_q[c] = tq;
     }
     __syncthreads();
-    const int cpg = C / G;
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
         float gs = 0.f, gq = 0.f;
-        for (int c = g * cpg; c < (g + 1) * cpg; ++c) { gs += sm_s[c]; gq += sm_q[c]; }
         float* dst = partial + (((size_t)b * nchunk + chunk) * G + g) * 2;
-        dst[0] = gs;
-        dst[1] = gq;
+        if (CEN) {
+            // the group's channels hold np values each, so Chan's merge of them is the mean of their means and
+            // M2 = sum M2_c + np sum (mean_c - mean)^2: two short passes over LDS, no division inside a dependent chain. The means are
+            // summed relative to the first channel's m0, a mean of np values: the group's pivot is ONE value and may lie sigmas off,
+            // and up to 256 sequential steps would round at the size of that distance every time.
+            // An empty chunk writes (0, 0) and is given the weight 0 by the merge in gn_apply_kernel.
+            const float m0 = sm_s[g * cpg];
+            for (int i = 0; i < cpg; ++i) { gs += sm_s[g * cpg + i] - m0; gq += sm_q[g * cpg + i]; }
+            gs *= __builtin_amdgcn_rcpf((float)cpg);
+            float dv = 0.f;
+            for (int i = 0; i < cpg; ++i) { const float d = (sm_s[g * cpg + i] - m0) - gs; dv += d * d; }
+            gq += (float)np * dv;
+            gs += m0;
+            dst[0] = np > 0 ? pivot_of(g * cpg) + gs : 0.f;
+            dst[1] = np > 0 ? gq : 0.f;
+        } else {
+            for (int c = g * cpg; c < (g + 1) * cpg; ++c) { gs += sm_s[c]; gq += sm_q[c]; }
+            dst[0] = gs;
+            dst[1] = gq;
+        }
     }
 }
 
@@ -114,7 +202,8 @@ template <bool SILU, bool X32 = false>
 __global__ void gn_apply_kernel(const h16_t* __restrict__ x, const float* __restrict__ partial,
                                 const h16_t* __restrict__ gamma, const h16_t* __restrict__ beta,
                                 h16_t* __restrict__ y, int HW, int C, int G, int nchunk,
-                                float eps, int pix_per_block, int KP, float* __restrict__ y32 = nullptr, int ysplit = 0) {
+                                float eps, int pix_per_block, int KP, float* __restrict__ y32 = nullptr, int ysplit = 0,
+                                int centered = 0) {
     // Block = (C/8)*KP threads like pass 1: a thread owns one 8-channel vector for all its pixels, so the per-channel
     // scale a_c = rstd_g * gamma_c and shift b_c = beta_c - mean_g * a_c live in 16 registers and the inner loop is one fma
     // (+ SiLU) per element -- no per-element group lookup (an integer division by a runtime C/G and two LDS reads before).
@@ -126,6 +215,11 @@ __global__ void gn_apply_kernel(const h16_t* __restrict__ x, const float* __rest
     {
         const int parts = nthr / G;                 // >= 2 for every supported shape (nthr >= 128, G <= 64)
         const int g = threadIdx.x % G, part = threadIdx.x / G;
+        // centered (the private format of gn_stats_kernel<.., CEN = true>): partial holds (mean_k, M2_k) per chunk; with P = the mean
+        // of chunk 0 (never empty) and n_k from the chunk geometry, gs = sum n_k (mean_k - P) and gq = sum M2_k + n_k (mean_k - P)^2
+        // are Chan's merge written as sums about P -- same fixed order as the public format, every term at the size of the spread.
+        const int per = (HW + nchunk - 1) / nchunk;
+        const float P = centered && part < parts ? partial[((size_t)b * nchunk * G + g) * 2] : 0.f;
         float gs = 0.f, gq = 0.f;
         if (part < parts) {
             for (int c0 = part; c0 < nchunk; c0 += 8 * parts) {   // 8 independent loads per round
@@ -136,8 +230,19 @@ __global__ void gn_apply_kernel(const h16_t* __restrict__ x, const float* __rest
                     t[u] = c < nchunk ? *reinterpret_cast<const float2*>(partial + (((size_t)b * nchunk + c) * G + g) * 2)
                                       : float2{0.f, 0.f};
                 }
+                if (centered) {
 #pragma unroll
-                for (int u = 0; u < 8; ++u) { gs += t[u].x; gq += t[u].y; }
+                    for (int u = 0; u < 8; ++u) {
+                        const int c = c0 + u * parts;
+                        const float nk = c < nchunk ? (float)max(min(HW, (c + 1) * per) - c * per, 0) * (float)cpg : 0.f;
+                        const float d = t[u].x - P;
+                        gs += nk * d;
+                        gq += t[u].y + nk * d * d;
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { gs += t[u].x; gq += t[u].y; }
+                }
             }
         }
         ps[threadIdx.x] = gs;
@@ -147,8 +252,15 @@ __global__ void gn_apply_kernel(const h16_t* __restrict__ x, const float* __rest
             gs = 0.f; gq = 0.f;
             for (int k = 0; k < parts; ++k) { gs += ps[k * G + threadIdx.x]; gq += pq[k * G + threadIdx.x]; }
             const float n = (float)HW * (float)cpg;
-            const float mu = gs / n;
-            const float var = fmaxf(gq / n - mu * mu, 0.f);
+            float mu, var;
+            if (centered) {
+                const float dm = gs / n;
+                mu = P + dm;
+                var = fmaxf((gq - gs * dm) / n, 0.f);
+            } else {
+                mu = gs / n;
+                var = fmaxf(gq / n - mu * mu, 0.f);
+            }
             mean[threadIdx.x] = mu;
             rstd[threadIdx.x] = rsqrtf(var + eps);
         }
@@ -292,16 +404,20 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const h16_t* __restrict__
         px += dq; cp += dr;
         if (cp >= hp) { cp -= hp; ++px; }
     }
-    float s = 0.f, q = 0.f;
+    // two passes over the registers: the variance is taken about the mean, so it keeps its bits whatever |mean| / sigma is
+    // (E[x^2] - mean^2 from one pass loses about 2 log2(|mean| / sigma) of them)
+    float s = 0.f;
 #pragma unroll
-    for (int u = 0; u < MAXP; ++u) {
-        const float lo = h16lo_to_f32(v[u]), hi = h16hi_to_f32(v[u]);   // padding entries are zeros
-        s += lo + hi;
-        q += lo * lo + hi * hi;
-    }
+    for (int u = 0; u < MAXP; ++u) s += h16lo_to_f32(v[u]) + h16hi_to_f32(v[u]);   // padding entries are zeros
     const float cnt = (float)HW * (float)cpg;
     const float mu = block_sum<4>(s, red) / cnt;
-    const float var = fmaxf(block_sum<4>(q, red) / cnt - mu * mu, 0.f);
+    float q = 0.f;
+#pragma unroll
+    for (int u = 0; u < MAXP; ++u) {
+        const float dl = h16lo_to_f32(v[u]) - mu, dh = h16hi_to_f32(v[u]) - mu;
+        q += (int)threadIdx.x + u * 256 < n ? dl * dl + dh * dh : 0.f;
+    }
+    const float var = block_sum<4>(q, red) / cnt;
     const float rs = rsqrtf(var + eps);
 #pragma unroll
     for (int u = 0; u < MAXP; ++u) {
@@ -1029,22 +1145,24 @@ int SPIDER_FN(spider_groupnorm_f32in_nhwc)(const float* x32, const float* partia
     if (KP < 1) KP = 1;
     const int threads = cv * KP;
     SPIDER_CHECK(threads <= 1024 && (threads >= 128 || threads >= 2 * G), "groupnorm_f32in: unsupported channel count for the block layout");
+    int centered = 0;
     if (!partial) {
         SPIDER_CHECK(ws, "groupnorm_f32in: ws is required without partial statistics");
         nchunk = gn_nchunk(HW);
-        gn_stats_kernel<true><<<dim3(nchunk, B), threads, (size_t)2 * KP * C * sizeof(float), (hipStream_t)stream>>>(
+        gn_stats_kernel<true, true><<<dim3(nchunk, B), threads, (size_t)2 * KP * C * sizeof(float), (hipStream_t)stream>>>(
             (const h16_t*)x32, ws, HW, C, G, nchunk, KP, nullptr, C, nullptr);
         SPIDER_LAUNCH_OK();
         partial = ws;
+        centered = 1;             // ws is private: (mean, M2) per chunk, independent of |mean| / sigma
     }
     SPIDER_CHECK(nchunk > 0, "groupnorm_f32in: nchunk");
     int ppb = 4 * KP;
     while ((long)B * ((HW + ppb - 1) / ppb) > 1024 && ppb < 64 * KP) ppb += 4 * KP;
     dim3 g2((HW + ppb - 1) / ppb, B);
     if (silu) gn_apply_kernel<true, true><<<g2, threads, 0, (hipStream_t)stream>>>((const h16_t*)x32, partial, (const h16_t*)gamma,
-                                                                             (const h16_t*)beta, (h16_t*)y, HW, C, G, nchunk, eps, ppb, KP, y32);
+                                                                             (const h16_t*)beta, (h16_t*)y, HW, C, G, nchunk, eps, ppb, KP, y32, 0, centered);
     else gn_apply_kernel<false, true><<<g2, threads, 0, (hipStream_t)stream>>>((const h16_t*)x32, partial, (const h16_t*)gamma,
-                                                                          (const h16_t*)beta, (h16_t*)y, HW, C, G, nchunk, eps, ppb, KP, y32);
+                                                                          (const h16_t*)beta, (h16_t*)y, HW, C, G, nchunk, eps, ppb, KP, y32, 0, centered);
     SPIDER_LAUNCH_OK();
     return 0;
 }
@@ -1077,8 +1195,9 @@ static int groupnorm_impl(const void* x, const void* x2, const void* gamma, cons
     const int threads = cv * KP;
     SPIDER_CHECK(threads <= 1024, "groupnorm: C too large");
     dim3 g1(nchunk, B);
-    gn_stats_kernel<false><<<g1, threads, (size_t)2 * KP * C * sizeof(float), (hipStream_t)stream>>>((const h16_t*)x, (float*)ws, HW, C,
-                                                                                       G, nchunk, KP, (const h16_t*)x2, C1, (h16_t*)cat);
+    // ws is private to this call: the centred (mean, M2) format, read back by gn_apply_kernel with centered = 1
+    gn_stats_kernel<false, true><<<g1, threads, (size_t)2 * KP * C * sizeof(float), (hipStream_t)stream>>>((const h16_t*)x, (float*)ws, HW,
+                                                                                             C, G, nchunk, KP, (const h16_t*)x2, C1, (h16_t*)cat);
     SPIDER_LAUNCH_OK();
     if (x2) x = cat;              // pass 2 reads the concatenated copy pass 1 has just written
     int ppb = 4 * KP;             // one round of 4 independent 16-byte loads per thread
@@ -1086,9 +1205,9 @@ static int groupnorm_impl(const void* x, const void* x2, const void* gamma, cons
     SPIDER_CHECK(threads >= 128 || threads >= 2 * G, "groupnorm: too few channels for the block layout");
     dim3 g2((HW + ppb - 1) / ppb, B);
     if (silu) gn_apply_kernel<true><<<g2, threads, 0, (hipStream_t)stream>>>((const h16_t*)x, (const float*)ws, (const h16_t*)gamma,
-                                                                       (const h16_t*)beta, (h16_t*)y, HW, C, G, nchunk, eps, ppb, KP);
+                                                                       (const h16_t*)beta, (h16_t*)y, HW, C, G, nchunk, eps, ppb, KP, nullptr, 0, 1);
     else gn_apply_kernel<false><<<g2, threads, 0, (hipStream_t)stream>>>((const h16_t*)x, (const float*)ws, (const h16_t*)gamma,
-                                                                    (const h16_t*)beta, (h16_t*)y, HW, C, G, nchunk, eps, ppb, KP);
+                                                                    (const h16_t*)beta, (h16_t*)y, HW, C, G, nchunk, eps, ppb, KP, nullptr, 0, 1);
     SPIDER_LAUNCH_OK();
     return 0;
 }
@@ -1204,22 +1323,24 @@ int SPIDER_FN(spider_groupnorm_f32in_split_nhwc)(const float* x32, const float* 
     if (KP < 1) KP = 1;
     const int threads = cv * KP;
     SPIDER_CHECK(threads <= 1024 && (threads >= 128 || threads >= 2 * G), "groupnorm_f32in_split: unsupported channel count for the block layout");
+    int centered = 0;
     if (!partial) {
         SPIDER_CHECK(ws, "groupnorm_f32in_split: ws is required without partial statistics");
         nchunk = gn_nchunk(HW);
-        gn_stats_kernel<true><<<dim3(nchunk, B), threads, (size_t)2 * KP * C * sizeof(float), (hipStream_t)stream>>>(
+        gn_stats_kernel<true, true><<<dim3(nchunk, B), threads, (size_t)2 * KP * C * sizeof(float), (hipStream_t)stream>>>(
             (const h16_t*)x32, ws, HW, C, G, nchunk, KP, nullptr, C, nullptr);
         SPIDER_LAUNCH_OK();
         partial = ws;
+        centered = 1;             // ws is private: (mean, M2) per chunk, independent of |mean| / sigma
     }
     SPIDER_CHECK(nchunk > 0, "groupnorm_f32in_split: nchunk");
     int ppb = 4 * KP;
     while ((long)B * ((HW + ppb - 1) / ppb) > 1024 && ppb < 64 * KP) ppb += 4 * KP;
     dim3 g2((HW + ppb - 1) / ppb, B);
     if (silu) gn_apply_kernel<true, true><<<g2, threads, 0, (hipStream_t)stream>>>((const h16_t*)x32, partial, (const h16_t*)gamma,
-                                                                             (const h16_t*)beta, (h16_t*)y2, HW, C, G, nchunk, eps, ppb, KP, nullptr, 1);
+                                                                             (const h16_t*)beta, (h16_t*)y2, HW, C, G, nchunk, eps, ppb, KP, nullptr, 1, centered);
     else gn_apply_kernel<false, true><<<g2, threads, 0, (hipStream_t)stream>>>((const h16_t*)x32, partial, (const h16_t*)gamma,
-                                                                          (const h16_t*)beta, (h16_t*)y2, HW, C, G, nchunk, eps, ppb, KP, nullptr, 1);
+                                                                          (const h16_t*)beta, (h16_t*)y2, HW, C, G, nchunk, eps, ppb, KP, nullptr, 1, centered);
     SPIDER_LAUNCH_OK();
     return 0;
 }
