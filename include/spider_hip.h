@@ -408,6 +408,30 @@ int spider_nhwc_to_nchw_f32(const float* x, float* y, int B, int C, int HW, floa
  * the random per-key keep decision): bit j % 64 of word j / 64 = (u[j] < thr) for j < n_valid, 0 beyond. u [n] fp32 on the device. */
 int spider_pack_keep_bits_f32(const float* u, void* words, int n, int n_valid, float thr, void* stream);
 
+/* ---- Stable Diffusion safety checker around the CLIP ViT (csrc/safety.hip; run_safety_checker, custom_sd.py:376-384, called at :658) ----
+ * Additive to ABI v4. The 16-bit format of these three is an argument (f16: 0 = bf16, 1 = IEEE half), not a second entry point.
+ * spider_clip_preprocess: numpy_to_pil + CLIPImageProcessor on the device. images [B,3,H,W] fp32 in [0,1] -> 8-bit as
+ *   (x * 255).round() (half-even) -> Pillow's antialiased BICUBIC resize, horizontal pass then vertical, each pass rounded to 8 bits and
+ *   clipped (22-bit fixed-point taps, Pillow's Resample.c) -> centre crop -> (v / 255 - mean_c) / std_c -> patch rows
+ *   rows [B * (crop / patch)^2, Kp] (16-bit), column (c * patch + dy) * patch + dx, columns 3 patch^2 .. Kp - 1 written as zeros (Kp = 3 patch^2
+ *   rounded up to a multiple of 8: the K of the patch-embedding GEMM). The tap tables depend only on (H, W, size, crop) and live on the
+ *   device: xbounds / ybounds [crop, 2] int32 = (first input index, tap count) of each output column / row INSIDE the crop window,
+ *   xtaps [crop, ks_x] / ytaps [crop, ks_y] int32 = round(w * 2^22), zero beyond the count. norm [6] fp32 = mean[3], std[3].
+ *   tmp: B * 3 * H * crop bytes (the 8-bit image between the passes). Two launches, no atomics. */
+int spider_clip_preprocess(const float* images, void* tmp, void* rows, const int* xbounds, const int* xtaps, int ks_x,
+                           const int* ybounds, const int* ytaps, int ks_y, const float* norm, int B, int H, int W, int crop, int patch,
+                           int Kp, int f16, void* stream);
+/* StableDiffusionSafetyChecker.forward (diffusers 0.25) after the ViT, one block per image: fp32 cosine similarity of image_embeds [B,D]
+ * against special_care_embeds [n_special,D] and concept_embeds [n_concept,D] (all 16-bit, D % 8 == 0); special-care concepts first, in
+ * index order, score = round(cos - thr + adjustment, 3) (half-even on x * 1000) with adjustment 0 until one scores > 0 and 0.01 from the
+ * next entry on; then every concept the same way; flags[b] = any concept score > 0. scores [B, n_special + n_concept] fp32
+ * (special-care first), flags [B] int32; n_special + n_concept <= 64. */
+int spider_safety_decide(const void* image_embeds, const void* concept_embeds, const void* special_care_embeds, const float* thr_concept,
+                         const float* thr_special, float* scores, int* flags, int B, int D, int n_concept, int n_special, int f16,
+                         void* stream);
+/* images [B, per_image] fp32 (per_image = C * H * W, a multiple of 4): every image with flags[b] != 0 becomes zeros, in place */
+int spider_image_blackout_f32(float* images, const int* flags, int B, long per_image, void* stream);
+
 
 /* ---- "precise" operand forms (ABI v4; UNetEngine(precise=True)) ----
  * north_star asks for UNet latents within 1e-3 relative of the reference; with every MFMA operand rounded to 11 significand bits one

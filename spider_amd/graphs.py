@@ -61,4 +61,4 @@ class GraphRunner:
         for dst, src in zip(static_in, tensors):
             dst.copy_(src)
         g.replay()
-        return out.clone()
+        return out.clone() if torch.is_tensor(out) else tuple(o.clone() for o in out)      # a tuple of tensors: the safety checker

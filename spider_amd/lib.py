@@ -109,6 +109,10 @@ SIGNATURES = {
     "spider_conv2d_small_cin_f32in_bf16": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
     "spider_conv2d_small_cout_f32in_bf16": (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
     "spider_latent_to_nhwc_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    # safety checker around the CLIP ViT (csrc/safety.hip): the 16-bit format is an argument
+    "spider_clip_preprocess": (_i, [_vp] * 5 + [_i, _vp, _vp, _i, _vp] + [_i] * 7 + [_vp]),
+    "spider_safety_decide": (_i, [_vp] * 7 + [_i] * 5 + [_vp]),
+    "spider_image_blackout_f32": (_i, [_vp, _vp, _i, _l, _vp]),
 }
 
 # the diffusion-side operators (gemm / conv / attention / UNet ops / fused cross-attention translation units) also exist as

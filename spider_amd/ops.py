@@ -1552,3 +1552,125 @@ def pack_keep_bits(u: torch.Tensor, thr: float, n_valid: int) -> torch.Tensor:
     words = torch.empty((n + 63) // 64, dtype=torch.int64, device=u.device)
     _lib.call("spider_pack_keep_bits_f32", _p(u), _p(words), n, int(n_valid), float(thr), _stream())
     return words
+
+
+# --------------------------------------------------------------------------- safety checker around the CLIP ViT (csrc/safety.hip)
+RESIZE_PRECISION_BITS = 22      # Pillow's 8-bit resampler: taps are round(w * 2^22), accumulated in int32
+
+
+def bicubic_taps(in_size: int, out_size: int, first: int = 0, count: Optional[int] = None):
+    """Pillow's `precompute_coeffs` + `normalize_coeffs_8bpc` (Resample.c) for the antialiased BICUBIC filter (a = -0.5, support
+    2 * max(scale, 1), taps normalised to sum 1, then round(w * 2^22) away from zero), for output indices [first, first + count).
+    -> (bounds int32 [count, 2] = (first input index, tap count), taps int32 [count, ks]). A pass whose size does not change is the
+    identity in Pillow (ImagingResample skips it): one tap of weight 2^22. Host arithmetic in double, as in C."""
+    import numpy as np
+    count = out_size - first if count is None else count
+    one = 1 << RESIZE_PRECISION_BITS
+    if in_size == out_size:
+        bounds = np.stack([np.arange(first, first + count), np.ones(count, dtype=np.int64)], 1).astype(np.int32)
+        return bounds, np.full((count, 1), one, dtype=np.int32)
+
+    def cubic(x):
+        x = abs(x)
+        if x < 1.0:
+            return ((-0.5 + 2.0) * x - (-0.5 + 3.0)) * x * x + 1
+        if x < 2.0:
+            return (((x - 5) * x + 8) * x - 4) * -0.5
+        return 0.0
+
+    scale = in_size / out_size
+    fscale = max(scale, 1.0)
+    support = 2.0 * fscale
+    ks = int(math.ceil(support)) * 2 + 1
+    bounds = np.zeros((count, 2), dtype=np.int32)
+    taps = np.zeros((count, ks), dtype=np.int32)
+    ss = 1.0 / fscale
+    for j in range(count):
+        center = (first + j + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [cubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = sum(w)
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        bounds[j] = (xmin, xmax)
+        taps[j, :xmax] = [int(-0.5 + v * one) if v < 0 else int(0.5 + v * one) for v in w]
+    assert (bounds[:, 0] >= 0).all() and (bounds[:, 0] + bounds[:, 1] <= in_size).all() and (bounds[:, 1] <= ks).all()
+    return bounds, taps
+
+
+def clip_resize_geometry(H: int, W: int, size: int, crop: int):
+    """(Hr, Wr, top, left) of CLIPImageProcessor: shortest edge -> `size`, long edge int(size * long / short) (transformers'
+    get_resize_output_image_size), centre crop top = (Hr - crop) // 2, left = (Wr - crop) // 2."""
+    if H <= W:
+        Hr, Wr = size, int(size * W / H)
+    else:
+        Hr, Wr = int(size * H / W), size
+    if crop > min(Hr, Wr):
+        raise NotImplementedError(f"crop_size {crop} larger than the resized image {Hr}x{Wr}: the padded centre crop is not implemented")
+    return Hr, Wr, (Hr - crop) // 2, (Wr - crop) // 2
+
+
+_CLIP_TABLES = {}
+
+
+def clip_preprocess_tables(H: int, W: int, size: int, crop: int, mean, std, device) -> dict:
+    """Device-resident tap tables + normalisation constants of spider_clip_preprocess for one image shape (built once per shape on
+    the host, outside stream capture: engines run an eager pass before they capture)."""
+    device = torch.device(device)
+    key = (H, W, size, crop, tuple(float(m) for m in mean), tuple(float(s) for s in std), device.type, device.index)
+    t = _CLIP_TABLES.get(key)
+    if t is None:
+        Hr, Wr, top, left = clip_resize_geometry(H, W, size, crop)
+        xb, xt = bicubic_taps(W, Wr, left, crop)
+        yb, yt = bicubic_taps(H, Hr, top, crop)
+        dv = lambda a, dt: torch.as_tensor(a, dtype=dt).contiguous().to(device)
+        t = dict(xb=dv(xb, torch.int32), xt=dv(xt, torch.int32), yb=dv(yb, torch.int32), yt=dv(yt, torch.int32),
+                 norm=dv(list(mean) + list(std), torch.float32), H=H, W=W, crop=crop, ks_x=xt.shape[1], ks_y=yt.shape[1])
+        _CLIP_TABLES[key] = t
+    return t
+
+
+def clip_preprocess(images, tables: dict, patch: int, dtype=BF16, out=None):
+    """images [B,3,H,W] fp32 in [0,1] (VAEDecoderEngine.decode's buffer) -> patch rows [B * (crop/patch)^2, Kp] of `dtype`,
+    Kp = 3 patch^2 rounded up to a multiple of 8, pad columns zero: numpy_to_pil + CLIPImageProcessor (Pillow BICUBIC) on the device."""
+    _chk(images, torch.float32, "images")
+    B, Cn, H, W = images.shape
+    if Cn != 3 or (H, W) != (tables["H"], tables["W"]):
+        raise ValueError(f"clip_preprocess: images {tuple(images.shape)} do not match the tables' [B,3,{tables['H']},{tables['W']}]")
+    crop = tables["crop"]
+    Kp = (3 * patch * patch + 7) // 8 * 8
+    if out is None:
+        out = torch.empty(B * (crop // patch) ** 2, Kp, dtype=dtype, device=images.device)
+    _, sfx = _h16(out)
+    tmp = torch.empty(B * 3 * H * crop, dtype=torch.uint8, device=images.device)
+    _lib.call("spider_clip_preprocess", _p(images), _p(tmp), _p(out), _p(tables["xb"]), _p(tables["xt"]), tables["ks_x"], _p(tables["yb"]),
+              _p(tables["yt"]), tables["ks_y"], _p(tables["norm"]), B, H, W, crop, patch, Kp, int(sfx == "f16"), _stream())
+    return out
+
+
+def safety_decide(image_embeds, concept_embeds, special_care_embeds, thr_concept, thr_special, scores=None, flags=None):
+    """-> (scores fp32 [B, n_special + n_concept] (special-care first), flags int32 [B]); see spider_safety_decide."""
+    dt, sfx = _h16(image_embeds)
+    _chk(image_embeds, dt, "image_embeds"); _chk(concept_embeds, dt, "concept_embeds"); _chk(special_care_embeds, dt, "special_care_embeds")
+    _chk(thr_concept, torch.float32, "thr_concept"); _chk(thr_special, torch.float32, "thr_special")
+    B, D = image_embeds.shape
+    n_c, n_s = concept_embeds.shape[0], special_care_embeds.shape[0]
+    assert concept_embeds.shape[1] == D and (n_s == 0 or special_care_embeds.shape[1] == D)
+    assert thr_concept.numel() == n_c and thr_special.numel() == n_s
+    if scores is None:
+        scores = torch.empty(B, n_s + n_c, dtype=torch.float32, device=image_embeds.device)
+    if flags is None:
+        flags = torch.empty(B, dtype=torch.int32, device=image_embeds.device)
+    _lib.call("spider_safety_decide", _p(image_embeds), _p(concept_embeds), _p(special_care_embeds) if n_s else None, _p(thr_concept),
+              _p(thr_special) if n_s else None, _p(scores), _p(flags), B, D, n_c, n_s, int(sfx == "f16"), _stream())
+    return scores, flags
+
+
+def image_blackout_(images, flags):
+    """images [B, ...] fp32, flags [B] int32 on the device: flagged images become zeros IN PLACE. -> images"""
+    _chk(images, torch.float32, "images"); _chk(flags, torch.int32, "flags")
+    B = images.shape[0]
+    assert flags.numel() == B
+    _lib.call("spider_image_blackout_f32", _p(images), _p(flags), B, images.numel() // B, _stream())
+    return images

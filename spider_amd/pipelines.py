@@ -9,8 +9,13 @@ following spider/models/custom_sd.py: __call__ :476-667, _encode_prompt :223-374
 prepare_latents :459-474, denoising loop :627-652, decode_latents :386-393. Everything numeric runs on the HIP
 engines (CLIPTextEngine, UNetEngine, VAEDecoderEngine); this file is host glue. Differences from the reference,
 all deliberate: models are loaded once per pipeline object (the reference reloads from disk in every decode call,
-spider_decoder.py:109,114); latents stay fp32 in HBM; the safety checker (an output filter, not on the numeric
-path) is not run.
+spider_decoder.py:109,114); latents stay fp32 in HBM.
+
+The safety checker (run_safety_checker, custom_sd.py:376-384, called at :658) runs on the device between the VAE and the copy to the
+host when the pipeline has one (spider_amd/safety.py: feature extractor, CLIP ViT, concept decision and black-out in one hipGraph):
+`from_pretrained` loads `safety_checker/` when the directory holds one, as the reference's call does, and `safety_checker=None`
+switches it off, as in diffusers. Flagged images come back black and `nsfw_content_detected` is a list of bool per image; without a
+checker it is None and nothing new is launched.
 """
 from __future__ import annotations
 
@@ -64,17 +69,22 @@ class StableDiffusionPipeline:
     vae_scale_factor = 8
 
     def __init__(self, unet: UNetEngine, vae: Optional[VAEDecoderEngine], text_encoder: Optional[CLIPTextEngine], tokenizer,
-                 scheduler=None, sample_size: int = 64):
+                 scheduler=None, sample_size: int = 64, safety_checker=None):
         self.unet, self.vae, self.text_encoder, self.tokenizer = unet, vae, text_encoder, tokenizer
         self.scheduler = scheduler or PNDMScheduler()
         self.sample_size = sample_size
         self.device = unet.device
+        self.safety_checker = safety_checker          # SafetyCheckerEngine or None (None: nothing new runs)
         if vae is not None:
             self.vae_scale_factor = 2 ** (len(vae.cfg.block_out) - 1)
 
+    _LOAD_CHECKER = object()       # from_pretrained's default: load safety_checker/ when the directory has one
+
     @classmethod
-    def from_pretrained(cls, path: str, torch_dtype=None, device="cuda:0", precise: int = 0, **unused):
-        """diffusers directory layout: unet/, vae/, text_encoder/, tokenizer/, scheduler/scheduler_config.json."""
+    def from_pretrained(cls, path: str, torch_dtype=None, device="cuda:0", precise: int = 0, safety_checker=_LOAD_CHECKER, **unused):
+        """diffusers directory layout: unet/, vae/, text_encoder/, tokenizer/, scheduler/scheduler_config.json, and optionally
+        safety_checker/ + feature_extractor/preprocessor_config.json. `safety_checker=None` loads no checker (as in diffusers); a
+        SafetyCheckerEngine passed in is used as it is."""
         from transformers import CLIPTokenizer
         sc = json.load(open(os.path.join(path, "scheduler", "scheduler_config.json")))
         sched = scheduler_from_config(sc)
@@ -82,10 +92,17 @@ class StableDiffusionPipeline:
         dt = engine_dtype(torch_dtype)
         # stream32: fp32 master of the residual stream (+ 2.9 % per UNet evaluation, 26 % closer to the fp32 oracle: DESIGN.md section 4);
         # precise = 1 / 2 (an extra keyword of this loader, 0 = off): the stream's consumers read the master -- inside north_star's 1e-3
+        if safety_checker is cls._LOAD_CHECKER:
+            safety_checker = None
+            if os.path.isdir(os.path.join(path, "safety_checker")):
+                from .safety import SafetyCheckerEngine, read_preprocess_config
+                safety_checker = SafetyCheckerEngine.from_pretrained(os.path.join(path, "safety_checker"), device, dtype=dt,
+                                                                     preprocess=read_preprocess_config(os.path.join(path, "feature_extractor")))
         return cls(UNetEngine.from_pretrained(os.path.join(path, "unet"), device, dtype=dt, stream32=True, precise=precise),
                    VAEDecoderEngine.from_pretrained(os.path.join(path, "vae"), device, scaling=0.18215, dtype=dt),   # custom_sd.py:388
                    CLIPTextEngine.from_pretrained(os.path.join(path, "text_encoder"), device, dtype=dt),
-                   CLIPTokenizer.from_pretrained(os.path.join(path, "tokenizer")), sched, ucfg.get("sample_size", 64))
+                   CLIPTokenizer.from_pretrained(os.path.join(path, "tokenizer")), sched, ucfg.get("sample_size", 64),
+                   safety_checker=safety_checker)
 
     def to(self, device=None, *a, **k):
         return self
@@ -139,6 +156,14 @@ class StableDiffusionPipeline:
         img = self.vae.decode(latents)                       # [B,3,H,W] fp32 in [0,1]
         return img.cpu().permute(0, 2, 3, 1).float().numpy()
 
+    def run_safety_checker(self, image_dev: torch.Tensor, use_graph: bool = True):
+        """image_dev [B,3,H,W] fp32 in [0,1] on the device -> (the images with the flagged ones black, list of bool per image), or
+        (image_dev, None) without a checker (custom_sd.py:376-384). The flags are the one host read."""
+        if self.safety_checker is None:
+            return image_dev, None
+        image_dev, flags = self.safety_checker(image_dev, use_graph=use_graph)
+        return image_dev, [bool(f) for f in flags.cpu().tolist()]
+
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str], None] = None, height: Optional[int] = None, width: Optional[int] = None,
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, negative_prompt=None,
@@ -167,10 +192,15 @@ class StableDiffusionPipeline:
         lat = denoise(self.unet, self.scheduler, lat, embeds, guidance_scale, num_inference_steps)
         if output_type == "latent":
             return PipelineOutput(lat)
-        image = self.decode_latents(lat)
+        has_nsfw = None
+        if self.safety_checker is None:
+            image = self.decode_latents(lat)
+        else:                                                # VAE -> checker -> host: the image leaves the device already filtered
+            image, has_nsfw = self.run_safety_checker(self.vae.decode(lat))
+            image = image.cpu().permute(0, 2, 3, 1).float().numpy()
         if output_type == "pil":
             image = numpy_to_pil(image)
-        return PipelineOutput(image) if return_dict else (image, None)
+        return PipelineOutput(image, has_nsfw) if return_dict else (image, has_nsfw)
 
 
 class AudioPipelineOutput:

@@ -246,7 +246,51 @@ def _(wq_gate_up, scale, x, norm_w=None, eps=1e-6):
     return x.new_empty(x.numel() // wq_gate_up.shape[1], wq_gate_up.shape[0] // 2)
 
 
-# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops and the FP8 GEMVs above are listed apart
+# ------------------------------------------------------------------------------------------ safety checker around the CLIP ViT
+@_op("clip_preprocess")
+def clip_preprocess(images: torch.Tensor, xbounds: torch.Tensor, xtaps: torch.Tensor, ybounds: torch.Tensor, ytaps: torch.Tensor,
+                    norm: torch.Tensor, patch: int, f16: bool) -> torch.Tensor:
+    """numpy_to_pil + CLIPImageProcessor on the device (run_safety_checker's feature extractor, custom_sd.py:376-384): images
+    [B,3,H,W] fp32 in [0,1] -> patch rows [B * (crop / patch)^2, Kp] bf16 / f16 for the ViT's patch-embedding GEMM. The int32 tap
+    tables (ops.clip_preprocess_tables: bounds [crop, 2], taps [crop, ks]) and norm [6] = mean, std live on the device."""
+    tables = dict(xb=xbounds, xt=xtaps, yb=ybounds, yt=ytaps, norm=norm, H=images.shape[2], W=images.shape[3], crop=xbounds.shape[0],
+                  ks_x=xtaps.shape[1], ks_y=ytaps.shape[1])
+    return ops.clip_preprocess(images.contiguous(), tables, patch, dtype=torch.float16 if f16 else BF16)
+
+
+@clip_preprocess.register_fake
+def _(images, xbounds, xtaps, ybounds, ytaps, norm, patch, f16):
+    crop = xbounds.shape[0]
+    return images.new_empty(images.shape[0] * (crop // patch) ** 2, (3 * patch * patch + 7) // 8 * 8, dtype=torch.float16 if f16 else BF16)
+
+
+@_op("safety_decide")
+def safety_decide(image_embeds: torch.Tensor, concept_embeds: torch.Tensor, special_care_embeds: torch.Tensor, thr_concept: torch.Tensor,
+                  thr_special: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """StableDiffusionSafetyChecker.forward after the ViT: -> (scores fp32 [B, n_special + n_concept], flags int32 [B])"""
+    return ops.safety_decide(image_embeds.contiguous(), concept_embeds, special_care_embeds, thr_concept, thr_special)
+
+
+@safety_decide.register_fake
+def _(image_embeds, concept_embeds, special_care_embeds, thr_concept, thr_special):
+    B = image_embeds.shape[0]
+    return (image_embeds.new_empty(B, concept_embeds.shape[0] + special_care_embeds.shape[0], dtype=torch.float32),
+            image_embeds.new_empty(B, dtype=torch.int32))
+
+
+@_op("image_blackout_", mutates=("images",))
+def image_blackout_(images: torch.Tensor, flags: torch.Tensor) -> None:
+    """every image of [B,3,H,W] fp32 whose flag is set becomes zeros, in place (custom_sd.py:376-384: flagged images come back black)"""
+    ops.image_blackout_(images, flags)
+
+
+@image_blackout_.register_fake
+def _(images, flags):
+    return None
+
+
+# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 GEMVs and the safety-checker ops above are listed apart
+SAFETY_OP_NAMES = ("clip_preprocess", "safety_decide", "image_blackout_")
 W8_OP_NAMES = ("gemv_w8", "gemv_swiglu_w8")
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
