@@ -432,6 +432,25 @@ int spider_safety_decide(const void* image_embeds, const void* concept_embeds, c
 /* images [B, per_image] fp32 (per_image = C * H * W, a multiple of 4): every image with flags[b] != 0 becomes zeros, in place */
 int spider_image_blackout_f32(float* images, const int* flags, int B, long per_image, void* stream);
 
+/* ---- Whisper log-mel features, the audio input of Qwen2.5-Omni (csrc/audio_features.hip; WhisperFeatureExtractor with
+ * padding="max_length", as Qwen2_5OmniProcessor calls it) ---- Additive to ABI v4.
+ * waves: fp32 clips packed one behind the other; clip b = waves[offsets[b] .. offsets[b] + lengths[b]) (int32 device arrays; a
+ *   length beyond n_samples is truncated). Per clip, as if zero-padded to n_samples: reflect pad n_fft / 2, frames of n_fft at hop,
+ *   periodic Hann, |X_k|^2, last frame dropped (cap = n_samples / hop frames), mel projection, log10(max(., 1e-10)),
+ *   max(., clip_max - 8), (. + 4) / 4. feat [B, mel, cap] fp32 and mask [B, cap] int32 (1 for frame f < ceil(length / hop)) are written
+ *   completely: frames whose window holds only padding get the floor value (max(clip_max - 8, -10) + 4) / 4 without being computed.
+ * table [n_fft, ldt] fp32, ldt = 64 G, G = ceil((n_fft / 2 + 1) / 32): columns [64 g, 64 g + 32) = w[n] cos(2 pi n k / n_fft),
+ *   [64 g + 32, 64 g + 64) = w[n] sin(2 pi n k / n_fft) for the bins k = 32 g .. 32 g + 31, zero columns beyond n_fft / 2;
+ *   fb [n_fft / 2 + 1, mel] fp32. n_fft even and <= 512, mel <= 128, hop <= n_fft, cap * hop <= n_samples.
+ * tile_max: B * max_tiles floats of scratch; max_tiles = ceil(F / spider_logmel_tile_frames()), F = the frames of the LONGEST clip
+ *   whose window reaches it, min(cap, ceil((length + n_fft / 2) / hop)): the host-known lengths size the grid. Two launches (frames x
+ *   DFT table and the mel projection on the fp32-input MFMA; then clip maximum, clamp, scale, floor fill, mask), no atomics, no
+ *   synchronisation: the result is a pure function of the inputs. */
+int spider_logmel_tile_frames(void);
+int spider_logmel_f32(const float* waves, const int* offsets, const int* lengths, const float* table, const float* fb, float* feat,
+                      int* mask, float* tile_max, int B, int n_samples, int n_fft, int hop, int mel, int cap, int ldt, int max_tiles,
+                      void* stream);
+
 
 /* ---- "precise" operand forms (ABI v4; UNetEngine(precise=True)) ----
  * north_star asks for UNet latents within 1e-3 relative of the reference; with every MFMA operand rounded to 11 significand bits one

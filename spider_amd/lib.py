@@ -113,6 +113,9 @@ SIGNATURES = {
     "spider_clip_preprocess": (_i, [_vp] * 5 + [_i, _vp, _vp, _i, _vp] + [_i] * 7 + [_vp]),
     "spider_safety_decide": (_i, [_vp] * 7 + [_i] * 5 + [_vp]),
     "spider_image_blackout_f32": (_i, [_vp, _vp, _i, _l, _vp]),
+    # Whisper log-mel features (csrc/audio_features.hip)
+    "spider_logmel_tile_frames": (_i, []),
+    "spider_logmel_f32": (_i, [_vp] * 8 + [_i] * 8 + [_vp]),
 }
 
 # the diffusion-side operators (gemm / conv / attention / UNet ops / fused cross-attention translation units) also exist as

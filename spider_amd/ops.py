@@ -1674,3 +1674,47 @@ def image_blackout_(images, flags):
     assert flags.numel() == B
     _lib.call("spider_image_blackout_f32", _p(images), _p(flags), B, images.numel() // B, _stream())
     return images
+
+
+# --------------------------------------------------------------------------- Whisper log-mel features (csrc/audio_features.hip)
+def logmel(waves, lengths, tables: dict, out=None, mask=None, offsets=None, lengths_dev=None):
+    """Packed fp32 waveforms -> (input_features [B, mel, cap] fp32, attention_mask [B, cap] int32), both written completely: what
+    WhisperFeatureExtractor returns for clips padded to n_samples (spider_amd/audio_features.py states the feature).
+    waves: 1-D fp32 on the device, the clips one behind the other; lengths: samples per clip ON THE HOST (they size the grid: only
+    frames whose window reaches the clip are computed); tables: audio_features.logmel_tables(cfg, device). offsets / lengths_dev:
+    the int32 device arrays the kernel reads; built here from `lengths` (clip b starts where clip b - 1 ends) when not given --
+    pass them to keep host -> device copies out of a graph capture. Two launches on the current stream, no synchronisation."""
+    _chk(waves, torch.float32, "waves")
+    dv = waves.device
+    lens = [min(max(int(n), 0), tables["n_samples"]) for n in lengths]
+    B, mel, cap, hop, n_fft = len(lens), tables["mel"], tables["cap"], tables["hop"], tables["n_fft"]
+    if B == 0:
+        raise ValueError("logmel: no clips")
+    if (offsets is None) != (lengths_dev is None):
+        raise ValueError("logmel: pass offsets and lengths_dev together")
+    if offsets is None:
+        offs = [0]
+        for n in lens[:-1]:
+            offs.append(offs[-1] + n)
+        if offs[-1] + lens[-1] > waves.numel():
+            raise ValueError(f"logmel: the clips hold {offs[-1] + lens[-1]} samples, waves has {waves.numel()}")
+        meta = torch.tensor([offs, lens], dtype=torch.int32).to(dv)
+        offsets, lengths_dev = meta[0], meta[1]
+    _chk(offsets, torch.int32, "offsets"); _chk(lengths_dev, torch.int32, "lengths_dev")
+    assert offsets.numel() == B and lengths_dev.numel() == B
+    _chk(tables["table"], torch.float32, "table"); _chk(tables["fb"], torch.float32, "fb")
+    ldt = tables["table"].shape[1]
+    assert tuple(tables["table"].shape) == (n_fft, 64 * ((n_fft // 2 + 32) // 32)) and tuple(tables["fb"].shape) == (n_fft // 2 + 1, mel)
+    if out is None:
+        out = torch.empty(B, mel, cap, dtype=torch.float32, device=dv)
+    if mask is None:
+        mask = torch.empty(B, cap, dtype=torch.int32, device=dv)
+    _chk(out, torch.float32, "out"); _chk(mask, torch.int32, "mask")
+    assert tuple(out.shape) == (B, mel, cap) and tuple(mask.shape) == (B, cap)
+    tf = _lib.load().spider_logmel_tile_frames()
+    frames = min(cap, -(-(max(lens) + n_fft // 2) // hop))          # frames of the longest clip whose window reaches it
+    max_tiles = max(1, -(-frames // tf))
+    tile_max = torch.empty(B, max_tiles, dtype=torch.float32, device=dv)
+    _lib.call("spider_logmel_f32", _p(waves), _p(offsets), _p(lengths_dev), _p(tables["table"]), _p(tables["fb"]), _p(out), _p(mask),
+              _p(tile_max), B, tables["n_samples"], n_fft, hop, mel, cap, ldt, max_tiles, _stream())
+    return out, mask

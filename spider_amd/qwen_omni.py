@@ -578,8 +578,11 @@ class QwenOmniThinker:
     `llm` is a LlamaEngine with cfg.mrope_section set; towers are optional (text-only prompts need none)."""
 
     def __init__(self, llm, vision: Optional[VisionTowerEngine] = None, audio: Optional[AudioTowerEngine] = None,
-                 token_ids: Optional[OmniTokenIds] = None):
+                 token_ids: Optional[OmniTokenIds] = None, logmel=None):
+        """logmel: the audio_features.LogMelEngine behind `audio_waveforms=`; built on first use with Qwen2.5-Omni's values and the
+        audio tower's mel count when not given (from_pretrained reads the checkpoint's preprocessor_config.json)."""
         self.llm, self.vision, self.audio = llm, vision, audio
+        self.logmel = logmel
         self.ids = token_ids or OmniTokenIds()
         self.merge = vision.cfg.merge if vision is not None else 2
 
@@ -596,9 +599,25 @@ class QwenOmniThinker:
         cfg = json.load(open(os.path.join(path, "config.json")))
         if max_batch < 1:
             raise ValueError("max_batch must be >= 1")
+        logmel = None
+        if load_audio and os.path.exists(os.path.join(path, "preprocessor_config.json")):
+            from .audio_features import LogMelEngine
+            logmel = LogMelEngine.from_pretrained(path, device)
         return cls(LlamaEngine.from_pretrained(path, device, max_batch=max_batch, max_len=max_len),
                    VisionTowerEngine.from_pretrained(path, device) if load_vision else None,
-                   AudioTowerEngine.from_pretrained(path, device) if load_audio else None, OmniTokenIds.from_hf_dict(cfg))
+                   AudioTowerEngine.from_pretrained(path, device) if load_audio else None, OmniTokenIds.from_hf_dict(cfg), logmel)
+
+    def _logmel_engine(self):
+        if self.logmel is None:
+            from .audio_features import LogMelConfig, LogMelEngine
+            self.logmel = LogMelEngine(LogMelConfig(feature_size=self.audio.cfg.mel), self.llm.device)
+        return self.logmel
+
+    def _waveform_frames(self, audio_waveforms) -> List[int]:
+        """valid mel frames per clip from the clips' lengths alone (host arithmetic)"""
+        from .audio_features import valid_frames
+        cfg = self._logmel_engine().cfg
+        return [valid_frames(len(a), cfg) for a in audio_waveforms]
 
     def _splice(self, emb: torch.Tensor, input_ids: torch.Tensor, token: int, feats: torch.Tensor, what: str) -> None:
         mask = (input_ids == token).to(emb.device)
@@ -610,13 +629,23 @@ class QwenOmniThinker:
     @torch.no_grad()
     def prepare_inputs(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None, pixel_values_videos=None,
                        video_grid_thw=None, input_features=None, feature_attention_mask=None, audio_feature_lengths=None,
-                       use_audio_in_video=False, video_second_per_grid=None):
-        """-> (inputs_embeds [B, S, H] bf16, position_ids [3, B, S] long). Same argument names as the processor emits."""
+                       use_audio_in_video=False, video_second_per_grid=None, audio_waveforms=None, sampling_rate=None):
+        """-> (inputs_embeds [B, S, H] bf16, position_ids [3, B, S] long). Same argument names as the processor emits, and
+        `audio_waveforms` (list of 1-D clips at `sampling_rate`, checked when given) in place of `input_features`: the log-mel
+        features are computed on the device and the frame counts come from the clips' lengths, so no device -> host read is added."""
         dv = self.llm.device
         input_ids = input_ids.to(dv)
         emb = self.llm.embed_tokens(input_ids)
         aud_lens = None
-        if input_features is not None:
+        if audio_waveforms is not None:
+            if input_features is not None:
+                raise ValueError("pass either audio_waveforms or input_features, not both")
+            if self.audio is None:
+                raise ValueError("audio_waveforms given but no audio tower loaded")
+            feats, _, aud_lens = self._logmel_engine()(list(audio_waveforms), sampling_rate)
+            feats = torch.cat([feats[b, :, :n] for b, n in enumerate(aud_lens)], 1)      # [mel, total valid frames]
+            self._splice(emb, input_ids, self.ids.audio, self.audio(feats, aud_lens), "audio")
+        elif input_features is not None:
             if self.audio is None:
                 raise ValueError("input_features given but no audio tower loaded")
             if feature_attention_mask is not None:     # [B, mel, frames] padded -> [mel, total valid frames]
@@ -670,7 +699,8 @@ class QwenOmniThinker:
                 list(self.DEFAULT_EOS) if self.llm.cfg.vocab > max(self.DEFAULT_EOS) else None)
         kw.setdefault("sync_every", 8)
         tower_keys = ("pixel_values", "image_grid_thw", "pixel_values_videos", "video_grid_thw", "input_features",
-                      "feature_attention_mask", "audio_feature_lengths", "use_audio_in_video", "video_second_per_grid")
+                      "feature_attention_mask", "audio_feature_lengths", "use_audio_in_video", "video_second_per_grid", "audio_waveforms",
+                      "sampling_rate")
         emb, pos = self.prepare_inputs(input_ids, attention_mask, **{k: kw.pop(k) for k in tower_keys if k in kw})
         kw.pop("spk", None); kw.pop("return_audio", None)                          # talker options: no speech on this path
         h = self.llm.prefill_begin(inputs_embeds=emb, position_ids=pos, attention_mask=attention_mask, max_new_tokens=max_new_tokens, **kw)
@@ -678,10 +708,15 @@ class QwenOmniThinker:
 
     def would_capture(self, input_ids, attention_mask=None, cache_set: int = 0, pixel_values=None, image_grid_thw=None,
                       pixel_values_videos=None, video_grid_thw=None, input_features=None, feature_attention_mask=None,
-                      audio_feature_lengths=None, output_hidden_states: bool = False, return_logits: bool = False, decode: bool = True, **kw):
+                      audio_feature_lengths=None, output_hidden_states: bool = False, return_logits: bool = False, decode: bool = True,
+                      audio_waveforms=None, **kw):
         """Would `generate(**inputs)` capture a hipGraph -- a tower graph for these grid_thw VALUES / audio lengths, or the decode step
         for this row count and KV cache set? Answered from the engines' own caches, so evictions and resets count. A pass that
         captures must not run beside another host thread that enqueues or allocates (SpiderFreeInfer runs it alone)."""
+        if audio_waveforms is not None and input_features is not None:
+            raise ValueError("pass either audio_waveforms or input_features, not both")
+        if audio_waveforms is not None and self.audio is not None and not self.audio.has_graph(self._waveform_frames(audio_waveforms)):
+            return True
         if input_features is not None and self.audio is not None:
             lens = feature_attention_mask.bool().sum(1).tolist() if feature_attention_mask is not None else audio_feature_lengths
             if not self.audio.has_graph(lens):

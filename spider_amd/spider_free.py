@@ -49,7 +49,7 @@ class SpiderFreeResult:
 class SpiderFreeInfer:
     def __init__(self, thinker, processor, decoder_infer=None, cfg=None, device="cuda:0", generate_kwargs: Optional[dict] = None,
                  pipelined: bool = False, process_mm_info=None, streams=None, depth: int = 2, mode: str = "spider_free_qwen",
-                 story_pipe=None, story_kwargs: Optional[dict] = None, mask_box_inputs=None):
+                 story_pipe=None, story_kwargs: Optional[dict] = None, mask_box_inputs=None, device_audio_features: bool = False):
         """thinker: QwenOmniThinker (`model` of the reference); processor: the checkpoint's Qwen2_5OmniProcessor or an object with its
         three methods (apply_chat_template / __call__ / batch_decode); decoder_infer: SpiderDecoderInfer (built from `cfg` when
         omitted); generate_kwargs: extra arguments of every `thinker.generate` call (the reference passes spk / use_audio_in_video; do_sample /
@@ -83,6 +83,15 @@ class SpiderFreeInfer:
             decoder_infer = SpiderDecoderInfer(cfg)
         self.model, self.processor, self.spider_decoder_infer = thinker, processor, decoder_infer
         self.device = torch.device(device)
+        # device_audio_features: the processor's WhisperFeatureExtractor is replaced, once, by the device extractor of
+        # spider_amd.audio_features (same call, same keys; input_features / feature_attention_mask arrive on the device).
+        if device_audio_features:
+            from .audio_features import DeviceWhisperFeatureExtractor, is_whisper_feature_extractor
+            fe = getattr(processor, "feature_extractor", None)
+            if not is_whisper_feature_extractor(fe):
+                raise ValueError("device_audio_features=True needs a processor whose feature_extractor is a WhisperFeatureExtractor, "
+                                 f"got {type(fe).__name__}")
+            processor.feature_extractor = DeviceWhisperFeatureExtractor.from_feature_extractor(fe, self.device)
         self.generate_kwargs = dict(generate_kwargs or {})
         self.process_mm_info = process_mm_info
         self.is_pipelined = bool(pipelined)

@@ -289,8 +289,28 @@ def _(images, flags):
     return None
 
 
-# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 GEMVs and the safety-checker ops above are listed apart
+# ------------------------------------------------------------------------------------------ Whisper log-mel features (audio input)
+@_op("logmel")
+def logmel(waves: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, max_length: int, table: torch.Tensor, fb: torch.Tensor,
+           n_samples: int, hop: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """WhisperFeatureExtractor(padding="max_length") on the device: packed fp32 waveforms + int32 offsets / lengths [B] ->
+    (input_features [B, mel, n_samples // hop] fp32, attention_mask [B, n_samples // hop] int32). max_length: the longest clip's
+    sample count, known on the host (it sizes the grid); table / fb: audio_features.logmel_tables."""
+    tables = dict(table=table, fb=fb, n_fft=table.shape[0], hop=hop, mel=fb.shape[1], n_samples=n_samples, cap=n_samples // hop)
+    B = offsets.shape[0]
+    return ops.logmel(waves.contiguous(), [max_length] * B, tables, offsets=offsets, lengths_dev=lengths)
+
+
+@logmel.register_fake
+def _(waves, offsets, lengths, max_length, table, fb, n_samples, hop):
+    B, cap = offsets.shape[0], n_samples // hop
+    return waves.new_empty(B, fb.shape[1], cap, dtype=torch.float32), waves.new_empty(B, cap, dtype=torch.int32)
+
+
+# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 GEMVs, the safety-checker ops and the audio
+# feature op above are listed apart
 SAFETY_OP_NAMES = ("clip_preprocess", "safety_decide", "image_blackout_")
+AUDIO_OP_NAMES = ("logmel",)
 W8_OP_NAMES = ("gemv_w8", "gemv_swiglu_w8")
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
