@@ -451,6 +451,23 @@ int spider_logmel_f32(const float* waves, const int* offsets, const int* lengths
                       int* mask, float* tile_max, int B, int n_samples, int n_fft, int hop, int mel, int cap, int ldt, int max_tiles,
                       void* stream);
 
+/* ---- Qwen2-VL image patch rows, the image input of Qwen2.5-Omni (csrc/image_features.hip; Qwen2VLImageProcessorPil: smart_resize
+ * with Pillow's antialiased BICUBIC, (v / 255 - mean) / std, merge-block patch order, the frame written `temporal` times) ----
+ * Additive to ABI v4.
+ * images: uint8 RGB, interleaved HWC, packed one behind the other. desc: int64 [n_images, 16] on the device, per image
+ *   {byte offset into images, H, W, Ho, Wo, x bounds offset, x taps offset, ks_x, y bounds offset, y taps offset, ks_y, first output
+ *   row, byte offset into tmp, first input row the vertical pass reads, number of such rows, 0}; Ho and Wo are multiples of
+ *   patch * merge. tabs: int32, the four tables of every image at the offsets the descriptor names: bounds [n_out, 2] = (first input
+ *   index, tap count), taps [n_out, ks] (Pillow's 22-bit fixed point; the tap count is a run-time value without a cap).
+ * lut: uint32 [3, 256], the output element of channel c and 8-bit value v (bf16 in the low half, or the fp32 word): built on the host,
+ *   so that the result carries the host processor's bits. tmp: sum_i 3 * rows_i * Wo_i bytes of scratch, each image's piece 4-byte aligned.
+ * rows [sum_i Ho_i Wo_i / patch^2, 3 * temporal * patch^2] bf16 (f32 = 0) or fp32 (f32 = 1), 16-byte aligned, every element written:
+ *   row ((gh / merge * (Gw / merge) + gw / merge) * merge + mh) * merge + mw behind the image's first row, column
+ *   ((c * temporal + t) * patch + dy) * patch + dx. max_h_items = max_i rows_i * Wo_i / 4 and max_tiles = max_i (Ho_i Wo_i) / (patch merge)^2
+ *   size the two grids. Two launches (horizontal pass to 8 bits; vertical pass + clip + lookup + patch rows), no synchronisation. */
+int spider_qwen_image_patches(const void* images, const long long* desc, const int* tabs, const void* lut, void* tmp, void* rows,
+                              int n_images, int patch, int merge, int temporal, long max_h_items, int max_tiles, int f32, void* stream);
+
 
 /* ---- "precise" operand forms (ABI v4; UNetEngine(precise=True)) ----
  * north_star asks for UNet latents within 1e-3 relative of the reference; with every MFMA operand rounded to 11 significand bits one

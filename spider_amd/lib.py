@@ -116,6 +116,8 @@ SIGNATURES = {
     # Whisper log-mel features (csrc/audio_features.hip)
     "spider_logmel_tile_frames": (_i, []),
     "spider_logmel_f32": (_i, [_vp] * 8 + [_i] * 8 + [_vp]),
+    # Qwen2-VL image patch rows (csrc/image_features.hip)
+    "spider_qwen_image_patches": (_i, [_vp] * 6 + [_i] * 4 + [_l] + [_i] * 2 + [_vp]),
 }
 
 # the diffusion-side operators (gemm / conv / attention / UNet ops / fused cross-attention translation units) also exist as

@@ -1718,3 +1718,113 @@ def logmel(waves, lengths, tables: dict, out=None, mask=None, offsets=None, leng
     _lib.call("spider_logmel_f32", _p(waves), _p(offsets), _p(lengths_dev), _p(tables["table"]), _p(tables["fb"]), _p(out), _p(mask),
               _p(tile_max), B, tables["n_samples"], n_fft, hop, mel, cap, ldt, max_tiles, _stream())
     return out, mask
+
+
+# --------------------------------------------------------------------------- Qwen2-VL image patch rows (csrc/image_features.hip)
+def qwen_smart_resize(height: int, width: int, factor: int = 28, min_pixels: int = 56 * 56, max_pixels: int = 14 * 14 * 4 * 1280):
+    """transformers' `smart_resize` of Qwen2-VL to the letter: both sides multiples of `factor` (Python's round: half to even), the
+    area within [min_pixels, max_pixels] (floor on the way down, ceil on the way up), ValueError beyond an aspect ratio of 200."""
+    if max(height, width) / min(height, width) > 200:
+        raise ValueError(f"absolute aspect ratio must be smaller than 200, got {max(height, width) / min(height, width)}")
+    h_bar = round(height / factor) * factor
+    w_bar = round(width / factor) * factor
+    if h_bar * w_bar > max_pixels:
+        beta = math.sqrt((height * width) / max_pixels)
+        h_bar = max(factor, math.floor(height / beta / factor) * factor)
+        w_bar = max(factor, math.floor(width / beta / factor) * factor)
+    elif h_bar * w_bar < min_pixels:
+        beta = math.sqrt(min_pixels / (height * width))
+        h_bar = math.ceil(height * beta / factor) * factor
+        w_bar = math.ceil(width * beta / factor) * factor
+    return h_bar, w_bar
+
+
+QWEN_DESC_WORDS = 16      # int64 words per image record of spider_qwen_image_patches (include/spider_hip.h lists the fields)
+_QWEN_TABLES = {}
+
+
+def qwen_image_tables(sizes, cfg, device) -> dict:
+    """What spider_qwen_image_patches reads for a batch of images of these `sizes` ((H, W), ...) under `cfg`
+    (image_features.ImagePatchConfig), built once per (sizes, cfg, device) on the host and cached -- outside stream capture, like
+    clip_preprocess_tables: per image the Pillow tap tables of both passes (bicubic_taps) in one int32 buffer and an int64 record
+    {input offset, H, W, Ho, Wo, table offsets and tap counts, first output row, offset into the 8-bit intermediate, the input rows the
+    vertical pass reads}; and the [3, 256] lookup table of (v * rescale_factor - mean) / std, computed as transformers' numpy `rescale`
+    and `normalize` compute it (double product rounded to fp32, then fp32 subtract and divide) and cast once per output format."""
+    import numpy as np
+    device = torch.device(device)
+    sizes = tuple((int(h), int(w)) for h, w in sizes)
+    if not sizes:
+        raise ValueError("qwen_image_tables: no images")
+    key = (sizes, cfg, device.type, device.index)
+    t = _QWEN_TABLES.get(key)
+    if t is not None:
+        return t
+    P, m, Tp = cfg.patch_size, cfg.merge_size, cfg.temporal_patch_size
+    S = P * m
+    if (P * P) % 4 or S % 4 or (3 * Tp * P * P) % 8:
+        raise NotImplementedError(f"patch_size {P} / merge_size {m} / temporal_patch_size {Tp}: patch_size^2 and patch_size * merge_size "
+                                  "must be multiples of 4 and a patch row a multiple of 8 elements")
+    desc = np.zeros((len(sizes), QWEN_DESC_WORDS), dtype=np.int64)
+    tabs, grid = [], []
+    n_tab = in_off = tmp_off = row0 = max_h = max_tiles = 0
+
+    def put(a):
+        nonlocal n_tab
+        at = n_tab
+        tabs.append(np.ascontiguousarray(a, dtype=np.int32).reshape(-1))
+        n_tab += tabs[-1].size
+        return at
+
+    for i, (H, W) in enumerate(sizes):
+        if H < 1 or W < 1:
+            raise ValueError(f"qwen_image_tables: image {i} is {H}x{W}")
+        Ho, Wo = qwen_smart_resize(H, W, S, cfg.min_pixels, cfg.max_pixels)
+        xb, xt = bicubic_taps(W, Wo)
+        yb, yt = bicubic_taps(H, Ho)
+        y_first, y_end = int(yb[:, 0].min()), int((yb[:, 0] + yb[:, 1]).max())
+        y_count = y_end - y_first
+        desc[i] = (in_off, H, W, Ho, Wo, put(xb), put(xt), xt.shape[1], put(yb), put(yt), yt.shape[1], row0, tmp_off, y_first, y_count, 0)
+        grid.append((1, Ho // P, Wo // P))
+        in_off += H * W * 3
+        tmp_off += 3 * y_count * Wo                          # a multiple of 4: Wo is one of patch_size * merge_size
+        row0 += (Ho // P) * (Wo // P)
+        max_h = max(max_h, y_count * (Wo // 4))
+        max_tiles = max(max_tiles, (Ho // S) * (Wo // S))
+    if len(cfg.image_mean) != 3 or len(cfg.image_std) != 3:
+        raise NotImplementedError("image_mean / image_std must hold 3 values")
+    x = (np.arange(256, dtype=np.uint8).astype(np.float64) * cfg.rescale_factor).astype(np.float32)      # transformers' rescale
+    lut = ((x[:, None] - np.array(cfg.image_mean, dtype=np.float32)) / np.array(cfg.image_std, dtype=np.float32)).T      # and normalize
+    lut = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.float32))
+    lut_bf16 = (lut.to(BF16).view(torch.int16).to(torch.int32) & 0xffff).contiguous()      # round to nearest even, once
+    t = dict(desc=torch.from_numpy(desc).to(device), tabs=torch.from_numpy(np.concatenate(tabs)).to(device),
+             lut={BF16: lut_bf16.to(device), torch.float32: lut.view(torch.int32).contiguous().to(device)}, sizes=sizes, grid=grid,
+             rows=row0, cols=3 * Tp * P * P, in_bytes=in_off, tmp_bytes=tmp_off, max_h_items=max_h, max_tiles=max_tiles,
+             patch=P, merge=m, temporal=Tp)
+    _QWEN_TABLES[key] = t
+    return t
+
+
+def qwen_image_patches(packed_u8, tables: dict, dtype=BF16, out=None):
+    """packed uint8 RGB images (interleaved HWC, one behind the other, on the device) -> pixel_values [rows, 3 Tp P^2] of `dtype`
+    (bf16, or fp32 with the host processor's bits): Qwen2VLImageProcessorPil on the device. tables: qwen_image_tables of the images'
+    sizes. Two launches on the current stream whatever the number of images, every element of `out` written."""
+    _chk(packed_u8, torch.uint8, "packed_u8")
+    if dtype not in tables["lut"]:
+        raise ValueError(f"qwen_image_patches: dtype must be torch.bfloat16 or torch.float32, got {dtype}")
+    if packed_u8.numel() != tables["in_bytes"]:
+        raise ValueError(f"qwen_image_patches: the images of sizes {tables['sizes']} hold {tables['in_bytes']} bytes, "
+                         f"packed_u8 has {packed_u8.numel()}")
+    dv = packed_u8.device
+    if out is None:
+        out = torch.empty(tables["rows"], tables["cols"], dtype=dtype, device=dv)
+    _chk(out, dtype, "out")
+    if tuple(out.shape) != (tables["rows"], tables["cols"]):
+        raise ValueError(f"qwen_image_patches: out must be [{tables['rows']}, {tables['cols']}], got {tuple(out.shape)}")
+    lut = tables["lut"][dtype]
+    _chk(tables["desc"], torch.int64, "desc"); _chk(tables["tabs"], torch.int32, "tabs"); _chk(lut, torch.int32, "lut")
+    assert tuple(tables["desc"].shape) == (len(tables["sizes"]), QWEN_DESC_WORDS) and lut.numel() == 3 * 256
+    tmp = torch.empty(max(tables["tmp_bytes"], 4), dtype=torch.uint8, device=dv)
+    _lib.call("spider_qwen_image_patches", _p(packed_u8), _p(tables["desc"]), _p(tables["tabs"]), _p(lut), _p(tmp), _p(out),
+              len(tables["sizes"]), tables["patch"], tables["merge"], tables["temporal"], tables["max_h_items"], tables["max_tiles"],
+              int(dtype == torch.float32), _stream())
+    return out

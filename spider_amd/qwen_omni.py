@@ -578,11 +578,13 @@ class QwenOmniThinker:
     `llm` is a LlamaEngine with cfg.mrope_section set; towers are optional (text-only prompts need none)."""
 
     def __init__(self, llm, vision: Optional[VisionTowerEngine] = None, audio: Optional[AudioTowerEngine] = None,
-                 token_ids: Optional[OmniTokenIds] = None, logmel=None):
+                 token_ids: Optional[OmniTokenIds] = None, logmel=None, image_patches=None):
         """logmel: the audio_features.LogMelEngine behind `audio_waveforms=`; built on first use with Qwen2.5-Omni's values and the
-        audio tower's mel count when not given (from_pretrained reads the checkpoint's preprocessor_config.json)."""
+        audio tower's mel count when not given (from_pretrained reads the checkpoint's preprocessor_config.json).
+        image_patches: the image_features.ImagePatchEngine behind `images=`; built on first use with Qwen2.5-Omni's pixel bounds and
+        the vision tower's patch geometry when not given (from_pretrained reads the same file)."""
         self.llm, self.vision, self.audio = llm, vision, audio
-        self.logmel = logmel
+        self.logmel, self.image_patches = logmel, image_patches
         self.ids = token_ids or OmniTokenIds()
         self.merge = vision.cfg.merge if vision is not None else 2
 
@@ -603,9 +605,14 @@ class QwenOmniThinker:
         if load_audio and os.path.exists(os.path.join(path, "preprocessor_config.json")):
             from .audio_features import LogMelEngine
             logmel = LogMelEngine.from_pretrained(path, device)
+        image_patches = None
+        if load_vision and os.path.exists(os.path.join(path, "preprocessor_config.json")):
+            from .image_features import ImagePatchEngine
+            image_patches = ImagePatchEngine.from_pretrained(path, device)
         return cls(LlamaEngine.from_pretrained(path, device, max_batch=max_batch, max_len=max_len),
                    VisionTowerEngine.from_pretrained(path, device) if load_vision else None,
-                   AudioTowerEngine.from_pretrained(path, device) if load_audio else None, OmniTokenIds.from_hf_dict(cfg), logmel)
+                   AudioTowerEngine.from_pretrained(path, device) if load_audio else None, OmniTokenIds.from_hf_dict(cfg), logmel,
+                   image_patches)
 
     def _logmel_engine(self):
         if self.logmel is None:
@@ -619,6 +626,21 @@ class QwenOmniThinker:
         cfg = self._logmel_engine().cfg
         return [valid_frames(len(a), cfg) for a in audio_waveforms]
 
+    OMNI_MAX_PIXELS = 12845056        # max_pixels of Qwen2.5-Omni's preprocessor_config.json (the class default is 28 * 28 * 1280)
+
+    def _image_engine(self):
+        if self.image_patches is None:
+            from .image_features import ImagePatchConfig, ImagePatchEngine
+            c = self.vision.cfg
+            self.image_patches = ImagePatchEngine(ImagePatchConfig(max_pixels=self.OMNI_MAX_PIXELS, patch_size=c.patch,
+                                                                   temporal_patch_size=c.temporal_patch, merge_size=c.merge), self.llm.device)
+        return self.image_patches
+
+    def _images_grid(self, images) -> torch.Tensor:
+        """image_grid_thw of raw images from their sizes alone (host arithmetic)"""
+        from .image_features import _as_list, image_sizes
+        return self._image_engine().grid_thw(image_sizes(_as_list(images)))
+
     def _splice(self, emb: torch.Tensor, input_ids: torch.Tensor, token: int, feats: torch.Tensor, what: str) -> None:
         mask = (input_ids == token).to(emb.device)
         n = int(mask.sum())
@@ -629,10 +651,13 @@ class QwenOmniThinker:
     @torch.no_grad()
     def prepare_inputs(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None, pixel_values_videos=None,
                        video_grid_thw=None, input_features=None, feature_attention_mask=None, audio_feature_lengths=None,
-                       use_audio_in_video=False, video_second_per_grid=None, audio_waveforms=None, sampling_rate=None):
+                       use_audio_in_video=False, video_second_per_grid=None, audio_waveforms=None, sampling_rate=None,
+                       images=None):
         """-> (inputs_embeds [B, S, H] bf16, position_ids [3, B, S] long). Same argument names as the processor emits, and
         `audio_waveforms` (list of 1-D clips at `sampling_rate`, checked when given) in place of `input_features`: the log-mel
-        features are computed on the device and the frame counts come from the clips' lengths, so no device -> host read is added."""
+        features are computed on the device and the frame counts come from the clips' lengths, so no device -> host read is added.
+        `images` (PIL / uint8 arrays, each its own size) in place of `pixel_values` + `image_grid_thw`: the patch rows are computed on
+        the device (image_features.ImagePatchEngine), the grid from the images' sizes on the host."""
         dv = self.llm.device
         input_ids = input_ids.to(dv)
         emb = self.llm.embed_tokens(input_ids)
@@ -656,6 +681,12 @@ class QwenOmniThinker:
                 aud_lens = [int(v) for v in audio_feature_lengths]
                 feats = input_features
             self._splice(emb, input_ids, self.ids.audio, self.audio(feats, aud_lens), "audio")
+        if images is not None:
+            if pixel_values is not None or image_grid_thw is not None:
+                raise ValueError("pass either images or pixel_values + image_grid_thw, not both")
+            if self.vision is None:
+                raise ValueError("images given but no vision tower loaded")
+            pixel_values, image_grid_thw = self._image_engine()(images)
         if pixel_values is not None:
             if self.vision is None:
                 raise ValueError("pixel_values given but no vision tower loaded")
@@ -700,7 +731,7 @@ class QwenOmniThinker:
         kw.setdefault("sync_every", 8)
         tower_keys = ("pixel_values", "image_grid_thw", "pixel_values_videos", "video_grid_thw", "input_features",
                       "feature_attention_mask", "audio_feature_lengths", "use_audio_in_video", "video_second_per_grid", "audio_waveforms",
-                      "sampling_rate")
+                      "sampling_rate", "images")
         emb, pos = self.prepare_inputs(input_ids, attention_mask, **{k: kw.pop(k) for k in tower_keys if k in kw})
         kw.pop("spk", None); kw.pop("return_audio", None)                          # talker options: no speech on this path
         h = self.llm.prefill_begin(inputs_embeds=emb, position_ids=pos, attention_mask=attention_mask, max_new_tokens=max_new_tokens, **kw)
@@ -709,7 +740,7 @@ class QwenOmniThinker:
     def would_capture(self, input_ids, attention_mask=None, cache_set: int = 0, pixel_values=None, image_grid_thw=None,
                       pixel_values_videos=None, video_grid_thw=None, input_features=None, feature_attention_mask=None,
                       audio_feature_lengths=None, output_hidden_states: bool = False, return_logits: bool = False, decode: bool = True,
-                      audio_waveforms=None, **kw):
+                      audio_waveforms=None, images=None, **kw):
         """Would `generate(**inputs)` capture a hipGraph -- a tower graph for these grid_thw VALUES / audio lengths, or the decode step
         for this row count and KV cache set? Answered from the engines' own caches, so evictions and resets count. A pass that
         captures must not run beside another host thread that enqueues or allocates (SpiderFreeInfer runs it alone)."""
@@ -720,6 +751,11 @@ class QwenOmniThinker:
         if input_features is not None and self.audio is not None:
             lens = feature_attention_mask.bool().sum(1).tolist() if feature_attention_mask is not None else audio_feature_lengths
             if not self.audio.has_graph(lens):
+                return True
+        if images is not None:
+            if pixel_values is not None or image_grid_thw is not None:
+                raise ValueError("pass either images or pixel_values + image_grid_thw, not both")
+            if self.vision is not None and not self.vision.has_graph(self._images_grid(images)):      # the images' sizes alone
                 return True
         for pv, grid in ((pixel_values, image_grid_thw), (pixel_values_videos, video_grid_thw)):
             if pv is not None and self.vision is not None and not self.vision.has_graph(grid):

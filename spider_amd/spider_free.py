@@ -49,7 +49,8 @@ class SpiderFreeResult:
 class SpiderFreeInfer:
     def __init__(self, thinker, processor, decoder_infer=None, cfg=None, device="cuda:0", generate_kwargs: Optional[dict] = None,
                  pipelined: bool = False, process_mm_info=None, streams=None, depth: int = 2, mode: str = "spider_free_qwen",
-                 story_pipe=None, story_kwargs: Optional[dict] = None, mask_box_inputs=None, device_audio_features: bool = False):
+                 story_pipe=None, story_kwargs: Optional[dict] = None, mask_box_inputs=None, device_audio_features: bool = False,
+                 device_image_features: bool = False):
         """thinker: QwenOmniThinker (`model` of the reference); processor: the checkpoint's Qwen2_5OmniProcessor or an object with its
         three methods (apply_chat_template / __call__ / batch_decode); decoder_infer: SpiderDecoderInfer (built from `cfg` when
         omitted); generate_kwargs: extra arguments of every `thinker.generate` call (the reference passes spk / use_audio_in_video; do_sample /
@@ -92,6 +93,15 @@ class SpiderFreeInfer:
                 raise ValueError("device_audio_features=True needs a processor whose feature_extractor is a WhisperFeatureExtractor, "
                                  f"got {type(fe).__name__}")
             processor.feature_extractor = DeviceWhisperFeatureExtractor.from_feature_extractor(fe, self.device)
+        # device_image_features: likewise the processor's Qwen2-VL image processor is replaced, once, by the device one of
+        # spider_amd.image_features (pixel_values arrive on the device as bf16, image_grid_thw stays on the host; videos= is not touched).
+        if device_image_features:
+            from .image_features import DeviceQwen2VLImageProcessor, is_qwen2vl_image_processor
+            ip = getattr(processor, "image_processor", None)
+            if not is_qwen2vl_image_processor(ip):
+                raise ValueError("device_image_features=True needs a processor whose image_processor is a Qwen2-VL image processor, "
+                                 f"got {type(ip).__name__}")
+            processor.image_processor = DeviceQwen2VLImageProcessor.from_image_processor(ip, self.device)
         self.generate_kwargs = dict(generate_kwargs or {})
         self.process_mm_info = process_mm_info
         self.is_pipelined = bool(pipelined)

@@ -307,10 +307,30 @@ def _(waves, offsets, lengths, max_length, table, fb, n_samples, hop):
     return waves.new_empty(B, fb.shape[1], cap, dtype=torch.float32), waves.new_empty(B, cap, dtype=torch.int32)
 
 
+# ------------------------------------------------------------------------------------------ Qwen2-VL image patch rows (image input)
+@_op("qwen_image_patches")
+def qwen_image_patches(packed_u8: torch.Tensor, desc: torch.Tensor, tabs: torch.Tensor, lut: torch.Tensor, rows: int, patch: int,
+                       merge: int, temporal: int, tmp_bytes: int, max_h_items: int, max_tiles: int, f32: bool) -> torch.Tensor:
+    """Qwen2VLImageProcessorPil on the device: packed uint8 HWC images -> pixel_values [rows, 3 temporal patch^2], bf16 or (f32) fp32.
+    desc / tabs / lut and the five integers are the entries of ops.qwen_image_tables for the images' sizes (lut: the one of the
+    output format)."""
+    dtype = torch.float32 if f32 else BF16
+    tables = dict(desc=desc, tabs=tabs, lut={dtype: lut}, sizes=(None,) * desc.shape[0], rows=rows, cols=3 * temporal * patch * patch,
+                  in_bytes=packed_u8.numel(), tmp_bytes=tmp_bytes, max_h_items=max_h_items, max_tiles=max_tiles, patch=patch, merge=merge,
+                  temporal=temporal)
+    return ops.qwen_image_patches(packed_u8.contiguous(), tables, dtype)
+
+
+@qwen_image_patches.register_fake
+def _(packed_u8, desc, tabs, lut, rows, patch, merge, temporal, tmp_bytes, max_h_items, max_tiles, f32):
+    return packed_u8.new_empty(rows, 3 * temporal * patch * patch, dtype=torch.float32 if f32 else BF16)
+
+
 # the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 GEMVs, the safety-checker ops and the audio
-# feature op above are listed apart
+# and image feature ops above are listed apart
 SAFETY_OP_NAMES = ("clip_preprocess", "safety_decide", "image_blackout_")
 AUDIO_OP_NAMES = ("logmel",)
+IMAGE_OP_NAMES = ("qwen_image_patches",)
 W8_OP_NAMES = ("gemv_w8", "gemv_swiglu_w8")
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
