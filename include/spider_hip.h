@@ -62,6 +62,20 @@ int spider_gemv_w8(const void* Wq, const float* scale, const void* x, void* out,
 int spider_gemv_swiglu_w8(const void* Wq_gate_up, const float* scale, const void* x, void* out, const void* norm_w, float eps,
                           int B, int I, int K, void* stream);
 
+/* Weight-only MXFP4 (OCP Microscaling FP4) forms of the same two calls for 1 <= B <= 4 (csrc/gemv_w4.hip), K % 32 == 0:
+ *   blocks [N, K / 2] bytes, row-major: byte j of row n holds weight 2 j in its low nibble and weight 2 j + 1 in its high nibble; a
+ *          nibble code c has sign bit 3 and magnitude {0, .5, 1, 1.5, 2, 3, 4, 6}[c & 7] (e2m1)
+ *   scales [N, K / 32] bytes, row-major, E8M0: weights 32 g .. 32 g + 31 of row n are multiplied by 2^(scales[n, g] - 127); bytes 1..254
+ *   out[b,n] = epilogue(sum_k xin[b,k] * W_eff[n,k])
+ * with the prologue and the epilogue of spider_gemv_bf16. The block scale is applied inside the conversion to bf16, which is exact.
+ * The fused RMSNorm needs the staged activations, B * ceil(K / 2048) * 4 KiB, within the LDS of a CU (160 KiB less 256 bytes).
+ * K % 32, B in 1..4 and null blocks / scales / x / out are refused (-1) before any launch. */
+int spider_gemv_w4(const void* blocks, const void* scales, const void* x, void* out, const void* bias, const void* res,
+                   const void* norm_w, float eps, int B, int N, int K, void* stream);
+/* blocks_gate_up [2 I, K / 2] = [gate rows | up rows], scales [2 I, K / 32]; out[b,i] = bf16(bf16(silu(bf16(g))) * bf16(u)) */
+int spider_gemv_swiglu_w4(const void* blocks_gate_up, const void* scales, const void* x, void* out, const void* norm_w, float eps,
+                          int B, int I, int K, void* stream);
+
 /* final norm + lm_head + greedy argmax (modeling_llama3.py:619,870-871; HF greedy loop driven from
  * spider.py:1492-1508). logits (bf16 [B,V]) optional. ws_val/ws_idx: B*spider_lm_head_nparts(V) floats/ints. */
 int spider_lm_head_nparts(int V);

@@ -45,11 +45,14 @@ from .graphs import capture as capture_graph
 BF16 = torch.bfloat16
 FP8 = torch.float8_e4m3fn       # OCP e4m3fn: max 448 (byte 0x7e), 1.0 = 0x38 -- the FP8 of gfx950, not MI300's e4m3fnuz
 FP8_MAX = 448.0
-WEIGHT_DTYPES = ("bf16", "fp8")
+WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
+MX_BLOCK = 32                   # weights per E8M0 scale of the OCP Microscaling formats
+FP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)      # e2m1 magnitudes by code & 7; bit 3 of the code is the sign
 
 
 def resolve_weight_dtype(weight_dtype) -> str:
-    """`weight_dtype` of LlamaEngine: "bf16" (default) or "fp8" (weight-only e4m3 stream for the decode GEMVs)"""
+    """`weight_dtype` of LlamaEngine: "bf16" (default), "fp8" (weight-only e4m3 stream for the decode GEMVs) or "mxfp4"
+    (weight-only e2m1 stream with one E8M0 scale per block of 32)"""
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype has to be one of {WEIGHT_DTYPES}, but is {weight_dtype!r}")
     return weight_dtype
@@ -82,6 +85,57 @@ def dequantize_fp8_rows(q: torch.Tensor, scale: torch.Tensor, dtype=BF16) -> tor
 
 
 dequantize = dequantize_fp8_rows
+
+
+def quantize_mxfp4(W: torch.Tensor):
+    """Weight-only OCP MXFP4: W [N, K], K % 32 == 0 -> (blocks uint8 [N, K / 2], scales uint8 [N, K / 32]).
+    Byte j of row n holds weight 2 j in its low nibble and weight 2 j + 1 in its high nibble; a nibble code c has sign bit 3 and
+    magnitude FP4_VALUES[c & 7]. Block g of row n (weights 32 g .. 32 g + 31) is multiplied by 2^(scales[n, g] - 127) (E8M0).
+    This is the layout of transformers.integrations.mxfp4 (FP4_VALUES, low nibble first, scales - 127, ldexp).
+        scale = 2^ceil(log2(amax / 6))  per block (byte 127 for an all-zero block; the exponent is clamped to [-125, 125], bytes
+        2 .. 252, so that every non-zero W_eff is a normal, finite bf16 number), which is quantize_fp8_rows' rule with e2m1's largest
+        value: no element saturates, and amax / scale lies in (3, 6] for every non-zero block.
+        Elements are rounded to nearest on the e2m1 grid, ties to the even significand: |v| / scale = 0.25, 0.75, 1.25, 1.75, 2.5,
+        3.5, 5 round to 0, 1, 1, 2, 2, 4, 4. The sign is kept (-0 is a legal code).
+    e2m1 has two significand bits and the scale is a power of two, so W_eff = dequantize_mxfp4(blocks, scales) is a bf16 matrix and
+    a model quantised this way IS a bf16 model with weights W_eff, as with quantize_fp8_rows. Quantising W_eff again returns W_eff,
+    but not always the same bytes: a block whose largest element lies in (3, 3.5) * scale rounds down to 3 * scale and then
+    requantises as (2 q, scale / 2). Round-to-nearest MXFP4 is coarse: ||W_eff - W|| / ||W|| = 11.8 % on N(0, 0.02^2) rows, where
+    quantize_fp8_rows has 2.6 %. Pure torch; runs wherever W lives."""
+    if W.dim() != 2 or W.shape[1] % MX_BLOCK:
+        raise ValueError(f"quantize_mxfp4: expected a [N, K] matrix with K % {MX_BLOCK} == 0, got {tuple(W.shape)}")
+    N, K = W.shape
+    Wf = W.detach().float().reshape(N, K // MX_BLOCK, MX_BLOCK)
+    amax = Wf.abs().amax(dim=2)
+    if not bool(torch.isfinite(amax).all()) or bool((amax > 6.0 * 2.0 ** 125).any()):
+        raise ValueError("quantize_mxfp4: entries have to be finite and at most 6 * 2^125 in magnitude")
+    # no rounded logarithm or division: amax = m * 2^e with m in [0.5, 1) and 6 = 0.75 * 2^3, so amax / 6 = (m / 0.75) * 2^(e - 3)
+    # lies in (2/3, 1] * 2^(e - 3) when m <= 0.75 and in (1, 4/3) * 2^(e - 3) otherwise
+    m, e = torch.frexp(amax)
+    e = (e - 3 + (m > 0.75).to(e.dtype)).clamp(-125, 125)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    a = Wf.abs() / torch.ldexp(torch.ones_like(amax), e)[:, :, None]     # exact: a power of two (a result below 2^-126 rounds to code 0 either way)
+    # code = number of midpoints passed; a tie goes up exactly when the upper neighbour has the even code
+    code = torch.zeros_like(a, dtype=torch.uint8)
+    for i, mid in enumerate((0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)):
+        code += ((a >= mid) if i & 1 else (a > mid)).to(torch.uint8)
+    code = (code | (torch.signbit(Wf).to(torch.uint8) << 3)).reshape(N, K // 2, 2)
+    blocks = code[:, :, 0] | (code[:, :, 1] << 4)
+    return blocks.contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(blocks: torch.Tensor, scales: torch.Tensor, dtype=BF16) -> torch.Tensor:
+    """W_eff [N, K] in `dtype` from blocks uint8 [N, K / 2] and scales uint8 [N, K / 32] (layout: quantize_mxfp4); exact in bf16
+    for scale bytes 2 .. 252"""
+    if blocks.dim() != 2 or scales.dim() != 2 or blocks.dtype != torch.uint8 or scales.dtype != torch.uint8 \
+            or blocks.shape[1] % (MX_BLOCK // 2) or tuple(scales.shape) != (blocks.shape[0], blocks.shape[1] // (MX_BLOCK // 2)):
+        raise ValueError(f"dequantize_mxfp4: expected uint8 blocks [N, K / 2] and scales [N, K / 32], got {tuple(blocks.shape)} "
+                         f"{blocks.dtype} and {tuple(scales.shape)} {scales.dtype}")
+    N, K = blocks.shape[0], blocks.shape[1] * 2
+    table = torch.tensor(FP4_VALUES + tuple(-v for v in FP4_VALUES), dtype=torch.float32, device=blocks.device)
+    codes = torch.stack([blocks & 15, blocks >> 4], dim=2).reshape(N, K // MX_BLOCK, MX_BLOCK)
+    vals = table[codes.long()]
+    return torch.ldexp(vals, (scales.to(torch.int32) - 127)[:, :, None]).reshape(N, K).to(dtype)
 
 
 @dataclass
@@ -569,6 +623,13 @@ class LlamaEngine:
     # 2638 / 2911 / 2996 / 3063, fp8 1823 / 2162 / 2536 / 3003 = 0.69 / 0.74 / 0.85 / 0.98 of it. 2 % at 4 rows is below the 3 % that
     # counts as a difference, so the range stops at 3.
     FP8_MAX_ROWS = 3
+    # weight_dtype="mxfp4" engines: decode graphs of up to this many rows stream the e2m1 bytes and E8M0 scales (csrc/gemv_w4.hip, which
+    # exists for 1..4 rows). Set by the same rule as FP8_MAX_ROWS from scripts/exp/mxfp4_decode_cost.py: the largest row count at which
+    # the MXFP4 step beats the bf16 route of the same row count by >= 3 %. Measured on MI355X, Qwen2.5-7B shapes at context 1536 (the
+    # three engines alternated in one process, 3 rounds of 96 replays, medians; rounds within 2 us), us per captured decode step by
+    # rows 1 / 2 / 3 / 4: bf16 2635 / 2910 / 2987 / 3067, fp8 1826 / 2156 / 2531 / 2986, mxfp4 1551 / 1876 / 2277 / 2872 =
+    # 0.59 / 0.65 / 0.76 / 0.94 of the bf16 step: 6.4 % at 4 rows counts, so the range is every row count the kernels exist for.
+    MXFP4_MAX_ROWS = 4
 
     def __init__(self, cfg: LLMConfig, weights: dict, device="cuda:0", max_batch: int = 1, max_len: int = 4096,
                  weight_dtype: str = "bf16"):
@@ -579,8 +640,15 @@ class LlamaEngine:
         FP8_MAX_ROWS rows run on W_eff as before, and decode steps of up to FP8_MAX_ROWS rows stream the bytes q (`*_q8`) and
         multiply the fp32 dot product by the row's scale (`*_s8`) -- the same function up to summation order, half the bytes per
         token. Memory: q is kept beside W_eff, about 1.5x the layer weights of a bf16 engine without fragment-major copies.
+        weight_dtype="mxfp4": the same construction on OCP MXFP4 (`quantize_mxfp4`: e2m1 nibbles, one E8M0 power-of-two scale per
+        block of 32 weights, 4.25 bits per weight). W_eff is again exactly a bf16 matrix and replaces the layer's matrices; decode
+        steps of up to MXFP4_MAX_ROWS rows stream the nibbles (`*_q4`) and the scale bytes (`*_e4`), which the kernel applies inside
+        the conversion. The format is coarse (11.8 % relative RMS weight error on N(0, 0.02^2) rows, FP8 2.6 %) and no text-quality
+        claim is made for it.
         The default "bf16" changes nothing: no tensor, no kernel, no graph key."""
         self.weight_dtype = resolve_weight_dtype(weight_dtype)
+        if self.weight_dtype == "mxfp4" and (cfg.hidden % 32 or cfg.inter % 32 or (cfg.n_q * cfg.head_dim) % 32):
+            raise ValueError("weight_dtype='mxfp4' needs hidden, inter and n_q * head_dim to be multiples of 32 (one E8M0 scale per block of 32 weights)")
         if self.weight_dtype == "fp8" and (cfg.hidden % 16 or cfg.inter % 16 or (cfg.n_q * cfg.head_dim) % 16):
             raise ValueError("weight_dtype='fp8' needs hidden, inter and n_q * head_dim to be multiples of 16 (16 weights per 16-byte load)")
         self.cfg, self.device = cfg, torch.device(device)
@@ -607,6 +675,11 @@ class LlamaEngine:
                     q, sc = quantize_fp8_rows(lw[k])
                     lw[k] = dequantize_fp8_rows(q, sc).contiguous()      # W_eff: what every bf16 kernel of this engine reads
                     lw[k + "_q8"], lw[k + "_s8"] = q.contiguous(), sc.contiguous()
+            elif self.weight_dtype == "mxfp4":
+                for k in ("w_qkv", "w_o", "w_gu", "w_down"):
+                    q, sc = quantize_mxfp4(lw[k])
+                    lw[k] = dequantize_mxfp4(q, sc).contiguous()         # W_eff, as above
+                    lw[k + "_q4"], lw[k + "_e4"] = q, sc
             self.layers.append(lw)
         # Batched decode (5..8 sequences per graph) streams a second, fragment-major copy of every decode weight (ops.repack_fm16:
         # 1 KiB contiguous per wave instruction of the skinny MFMA kernels). Memory is laid out for 288 GB of HBM: the copy
@@ -655,7 +728,7 @@ class LlamaEngine:
     def from_pretrained(cls, path: str, device="cuda:0", max_batch=1, max_len=4096, weight_dtype="bf16"):
         """Load an HF checkpoint directory: config.json + model.safetensors(.index.json + shards) or pytorch_model.bin
         (spider_amd/checkpoint.py). From a Qwen2.5-Omni directory only `thinker.model.*` / `thinker.lm_head.*` are read.
-        weight_dtype="fp8" quantises the layer matrices at load (see the constructor)."""
+        weight_dtype="fp8" / "mxfp4" quantise the layer matrices at load (see the constructor)."""
         from .checkpoint import load_state_dict, read_config
 
         def keep(k: str):
@@ -805,11 +878,18 @@ class LlamaEngine:
         w8 = self.weight_dtype == "fp8" and B <= min(self.FP8_MAX_ROWS, ops.W8_MAX_ROWS)
         fuse_norm = not fm and B < 5      # the row-major GEMV folds the RMSNorm for up to 4 rows; the skinny MFMA GEMM (fm) carries it in its weights
         w8_fuse = w8 and ops.w8_norm_fits(B, c.hidden)     # (a hidden size beyond the kernel's LDS budget: RMSNorm in its own launch)
+        # MXFP4 engines: the same four GEMVs on the e2m1 bytes and their block scales, up to MXFP4_MAX_ROWS rows
+        w4 = self.weight_dtype == "mxfp4" and B <= min(self.MXFP4_MAX_ROWS, ops.W4_MAX_ROWS)
+        w4_fuse = w4 and ops.w4_norm_fits(B, c.hidden)
         for l, lw in enumerate(self.layers):
             if w8 and w8_fuse:
                 ops.gemv_w8(lw["w_qkv_q8"], lw["w_qkv_s8"], h, bias=lw["b_qkv"], norm_w=lw["ln1"], eps=c.eps, out=st["qkv"])
             elif w8:
                 ops.gemv_w8(lw["w_qkv_q8"], lw["w_qkv_s8"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), bias=lw["b_qkv"], out=st["qkv"])
+            elif w4 and w4_fuse:
+                ops.gemv_w4(lw["w_qkv_q4"], lw["w_qkv_e4"], h, bias=lw["b_qkv"], norm_w=lw["ln1"], eps=c.eps, out=st["qkv"])
+            elif w4:
+                ops.gemv_w4(lw["w_qkv_q4"], lw["w_qkv_e4"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), bias=lw["b_qkv"], out=st["qkv"])
             elif fuse_norm:
                 ops.gemv(lw["w_qkv"], h, bias=lw["b_qkv"], norm_w=lw["ln1"], eps=c.eps, out=st["qkv"])
             elif fm:
@@ -831,6 +911,13 @@ class LlamaEngine:
                 else:
                     ops.gemv_swiglu_w8(lw["w_gu_q8"], lw["w_gu_s8"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
                 h = ops.gemv_w8(lw["w_down_q8"], lw["w_down_s8"], st["act"], res=h1, out=st["h2"][l & 1])
+            elif w4:
+                h1 = ops.gemv_w4(lw["w_o_q4"], lw["w_o_e4"], st["attn"], res=h, out=st["h1"])
+                if w4_fuse:
+                    ops.gemv_swiglu_w4(lw["w_gu_q4"], lw["w_gu_e4"], h1, norm_w=lw["ln2"], eps=c.eps, out=st["act"])
+                else:
+                    ops.gemv_swiglu_w4(lw["w_gu_q4"], lw["w_gu_e4"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
+                h = ops.gemv_w4(lw["w_down_q4"], lw["w_down_e4"], st["act"], res=h1, out=st["h2"][l & 1])
             elif fm:
                 h1 = ops.gemv_fm(lw["w_o_fm"], st["attn"], c.hidden, res=h, out=st["h1"])
                 ops.gemv_swiglu_fm(lw["w_gu_fm"], h1, out=st["act"], norm_eps=c.eps)

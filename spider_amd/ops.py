@@ -335,6 +335,66 @@ def gemv_swiglu_w8(Wq_gate_up, scale, x, norm_w=None, eps=0.0, out=None):
     return out
 
 
+W4_LDS_MAX_DEFAULT = 160 * 1024 - 256  # bytes of staged activations per block (csrc/gemv_w4.hip: W4_LDS_BUDGET_BYTES)
+W4_MAX_ROWS = 4                # rows the weight-only MXFP4 GEMVs exist for
+W4_LDS_MAX = min(int(_os.environ.get("SPIDER_W4_LDS_MAX", "0")) or W4_LDS_MAX_DEFAULT, 160 * 1024 - 256)   # mirror of csrc/gemv_w4.hip
+
+
+def w4_norm_fits(B: int, K: int) -> bool:
+    """True when gemv_w4 / gemv_swiglu_w4 can fuse the RMSNorm for B rows of K: the staged activations (rows padded to whole
+    2048-element chunks) fit the kernel's LDS budget (csrc/gemv_w4.hip: W4_LDS_BUDGET)"""
+    return B * ((K + 2047) // 2048) * 4096 <= W4_LDS_MAX
+
+
+def _chk_w4(blocks, scales, x, name):
+    _chk(blocks, torch.uint8, name); _chk(scales, torch.uint8, "scales"); _chk(x, BF16, "x")
+    if blocks.dim() != 2 or blocks.shape[1] % 16 or scales.dim() != 2 or tuple(scales.shape) != (blocks.shape[0], blocks.shape[1] // 16):
+        raise ValueError(f"{name}: expected [N, K / 2] bytes (K % 32 == 0) with scales [N, K / 32], got {tuple(blocks.shape)} and "
+                         f"{tuple(scales.shape)}")
+    K = blocks.shape[1] * 2
+    if x.shape[-1] != K:
+        raise ValueError(f"{name}: x[..., {x.shape[-1]}] vs {name}[{blocks.shape[0]}, {K} / 2]")
+    B = x.numel() // K
+    if not 1 <= B <= W4_MAX_ROWS:
+        raise ValueError(f"{name}: {B} rows of x, the MXFP4 GEMVs exist for 1..{W4_MAX_ROWS}")
+    return K, B
+
+
+def gemv_w4(blocks, scales, x, bias=None, res=None, norm_w=None, eps=0.0, out=None):
+    """`gemv` on weight-only MXFP4 (llm.quantize_mxfp4): blocks [N, K / 2] uint8, two e2m1 codes per byte, low nibble first;
+    scales [N, K / 32] uint8, E8M0, bytes 1..254. out[b,n] = sum_k xin[b,k] W_eff[n,k] (+bias) (+res) with
+    W_eff[n,k] = e2m1(code) * 2^(scales[n, k / 32] - 127), the scale applied inside the conversion. 1 <= B <= 4, K % 32 == 0."""
+    K, B = _chk_w4(blocks, scales, x, "blocks")
+    N = blocks.shape[0]
+    for t, n, cnt in ((bias, "bias", N), (res, "res", B * N), (norm_w, "norm_w", K)):
+        if t is not None:
+            _chk(t, BF16, n)
+            assert t.numel() == cnt, f"{n}: expected {cnt} elements"
+    if out is None:
+        out = torch.empty(B, N, dtype=BF16, device=x.device)
+    _chk(out, BF16, "out")
+    assert out.numel() == B * N
+    _lib.call("spider_gemv_w4", _p(blocks), _p(scales), _p(x), _p(out), _p(bias), _p(res), _p(norm_w), float(eps), B, N, K, _stream())
+    return out
+
+
+def gemv_swiglu_w4(blocks_gate_up, scales, x, norm_w=None, eps=0.0, out=None):
+    """`gemv_swiglu` on weight-only MXFP4: blocks_gate_up [2 I, K / 2] = [gate rows | up rows], scales [2 I, K / 32].
+    1 <= B <= 4, K % 32 == 0."""
+    K, B = _chk_w4(blocks_gate_up, scales, x, "blocks_gate_up")
+    I = blocks_gate_up.shape[0] // 2
+    assert blocks_gate_up.shape[0] == 2 * I
+    if norm_w is not None:
+        _chk(norm_w, BF16, "norm_w")
+        assert norm_w.numel() == K
+    if out is None:
+        out = torch.empty(B, I, dtype=BF16, device=x.device)
+    _chk(out, BF16, "out")
+    assert out.numel() == B * I
+    _lib.call("spider_gemv_swiglu_w4", _p(blocks_gate_up), _p(scales), _p(x), _p(out), _p(norm_w), float(eps), B, I, K, _stream())
+    return out
+
+
 def repack_fm16(W: torch.Tensor, norm_w: Optional[torch.Tensor] = None) -> torch.Tensor:
     """W [N, K] bf16 (K % 64 == 0); with norm_w [K] the copy holds bf16(W * norm_w) for the kernels' fold_rmsnorm form.
     W -> fragment-major copy [ceil(N/16), K/64, 2, 64, 8] for the *_fm kernels: piece (rg, kb, sx)

@@ -246,6 +246,34 @@ def _(wq_gate_up, scale, x, norm_w=None, eps=1e-6):
     return x.new_empty(x.numel() // wq_gate_up.shape[1], wq_gate_up.shape[0] // 2)
 
 
+# ------------------------------------------------------------------------------------------ weight-only MXFP4 decode GEMVs
+@_op("gemv_w4")
+def gemv_w4(blocks: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, bias: Optional[torch.Tensor] = None,
+            res: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6) -> torch.Tensor:
+    """nn.Linear at decode on weight-only MXFP4: blocks [N, K / 2] uint8 (two e2m1 codes per byte, low nibble first), scales
+    [N, K / 32] uint8 (E8M0); x [B <= 4, K] bf16 -> [B, N] bf16 = xin @ W_eff^T (+bias) (+res), xin = RMSNorm(x) * norm_w when
+    norm_w is given"""
+    return ops.gemv_w4(blocks, scales, x.contiguous(), bias=bias, res=res, norm_w=norm_w, eps=eps)
+
+
+@gemv_w4.register_fake
+def _(blocks, scales, x, bias=None, res=None, norm_w=None, eps=1e-6):
+    return x.new_empty(x.numel() // (2 * blocks.shape[1]), blocks.shape[0])
+
+
+@_op("gemv_swiglu_w4")
+def gemv_swiglu_w4(blocks_gate_up: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, norm_w: Optional[torch.Tensor] = None,
+                   eps: float = 1e-6) -> torch.Tensor:
+    """LlamaMLP gate / up + SiLU * mul on weight-only MXFP4: blocks_gate_up [2 I, K / 2] = [gate rows | up rows], scales
+    [2 I, K / 32]; -> [B <= 4, I]"""
+    return ops.gemv_swiglu_w4(blocks_gate_up, scales, x.contiguous(), norm_w=norm_w, eps=eps)
+
+
+@gemv_swiglu_w4.register_fake
+def _(blocks_gate_up, scales, x, norm_w=None, eps=1e-6):
+    return x.new_empty(x.numel() // (2 * blocks_gate_up.shape[1]), blocks_gate_up.shape[0] // 2)
+
+
 # ------------------------------------------------------------------------------------------ safety checker around the CLIP ViT
 @_op("clip_preprocess")
 def clip_preprocess(images: torch.Tensor, xbounds: torch.Tensor, xtaps: torch.Tensor, ybounds: torch.Tensor, ytaps: torch.Tensor,
@@ -326,12 +354,13 @@ def _(packed_u8, desc, tabs, lut, rows, patch, merge, temporal, tmp_bytes, max_h
     return packed_u8.new_empty(rows, 3 * temporal * patch * patch, dtype=torch.float32 if f32 else BF16)
 
 
-# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 GEMVs, the safety-checker ops and the audio
+# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 and MXFP4 GEMVs, the safety-checker ops and the audio
 # and image feature ops above are listed apart
 SAFETY_OP_NAMES = ("clip_preprocess", "safety_decide", "image_blackout_")
 AUDIO_OP_NAMES = ("logmel",)
 IMAGE_OP_NAMES = ("qwen_image_patches",)
 W8_OP_NAMES = ("gemv_w8", "gemv_swiglu_w8")
+W4_OP_NAMES = ("gemv_w4", "gemv_swiglu_w4")
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
             "conv2d_nhwc", "attn_self", "attn_cross_kv77", "attn_consistent", "geglu", "cfg_step")
