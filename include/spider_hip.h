@@ -101,6 +101,24 @@ int spider_lm_head_argmax_proc_bf16(const void* W, const void* x, const void* no
                                     void* ws_val, void* ws_idx, const void* seen, const void* ban, const float* penalty,
                                     const int* min_new, const int* eos_ids, const int* n_eos, const int* n_hist, int B, int V,
                                     int K, void* stream);
+/* Weight-only FP8 / MXFP4 forms of the two row-major lm_head entry points above for 1 <= B <= 4 (csrc/lm_head_wq.hip): the same
+ * final norm, bf16-rounded logits, processors, tie rule, logits output and workspaces, with the vocabulary matrix streamed as
+ *   _w8: q [V, K] OCP e4m3fn bytes and scale [V] fp32 (layout of spider_gemv_w8), K % 16 == 0;
+ *   _w4: blocks [V, K / 2] e2m1 nibbles and scales [V, K / 32] E8M0 bytes (layout of spider_gemv_w4), K % 32 == 0.
+ * The fused RMSNorm (norm_w != NULL) needs the staged activations within the LDS budget of spider_gemv_w8 / _w4. K, B in 1..4,
+ * null q / scale / x / out_ids / workspaces and a fused norm beyond the budget are refused (-1) before any launch. */
+int spider_lm_head_argmax_w8(const void* q, const void* scale, const void* x, const void* norm_w, float eps, int* out_ids,
+                             void* logits, void* ws_val, void* ws_idx, int B, int V, int K, void* stream);
+int spider_lm_head_argmax_proc_w8(const void* q, const void* scale, const void* x, const void* norm_w, float eps, int* out_ids,
+                                  void* logits, void* ws_val, void* ws_idx, const void* seen, const void* ban,
+                                  const float* penalty, const int* min_new, const int* eos_ids, const int* n_eos,
+                                  const int* n_hist, int B, int V, int K, void* stream);
+int spider_lm_head_argmax_w4(const void* blocks, const void* scales, const void* x, const void* norm_w, float eps, int* out_ids,
+                             void* logits, void* ws_val, void* ws_idx, int B, int V, int K, void* stream);
+int spider_lm_head_argmax_proc_w4(const void* blocks, const void* scales, const void* x, const void* norm_w, float eps,
+                                  int* out_ids, void* logits, void* ws_val, void* ws_idx, const void* seen, const void* ban,
+                                  const float* penalty, const int* min_new, const int* eos_ids, const int* n_eos,
+                                  const int* n_hist, int B, int V, int K, void* stream);
 /* spider_decode_advance_i32 + bit next_ids[b] of seen [B, ceil(V/32)] set (ids outside [0, V) set nothing) */
 int spider_decode_advance_seen_i32(const int* next_ids, int* cur_ids, int* pos, int* slot, int* kv_end, int* hist, int* n_hist,
                                    void* seen, int V, int cap, int B, void* stream);

@@ -40,6 +40,10 @@ SIGNATURES = {
     "spider_decode_advance_i32": (_i, [_vp] * 7 + [_i, _i, _vp]),
     "spider_lm_head_argmax_bf16": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "spider_lm_head_argmax_proc_bf16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 11 + [_i, _i, _i, _vp]),
+    "spider_lm_head_argmax_w8": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "spider_lm_head_argmax_proc_w8": (_i, [_vp, _vp, _vp, _vp, _f] + [_vp] * 11 + [_i, _i, _i, _vp]),
+    "spider_lm_head_argmax_w4": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "spider_lm_head_argmax_proc_w4": (_i, [_vp, _vp, _vp, _vp, _f] + [_vp] * 11 + [_i, _i, _i, _vp]),
     "spider_decode_advance_seen_i32": (_i, [_vp] * 8 + [_i, _i, _i, _vp]),
     "spider_token_bitmap_set_i32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "spider_ngram_ban_i32": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),

@@ -58,6 +58,14 @@ def resolve_weight_dtype(weight_dtype) -> str:
     return weight_dtype
 
 
+def resolve_lm_head_dtype(lm_head_dtype) -> str:
+    """`lm_head_dtype` of LlamaEngine: "bf16" (default), "fp8" or "mxfp4" (weight-only stream of the lm_head at decode, in the
+    formats of `weight_dtype` and independent of it)"""
+    if lm_head_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"lm_head_dtype has to be one of {WEIGHT_DTYPES}, but is {lm_head_dtype!r}")
+    return lm_head_dtype
+
+
 def quantize_fp8_rows(W: torch.Tensor):
     """Per-row weight-only FP8: W [N, K] -> (q [N, K] float8_e4m3fn, scale [N] float32) with
         scale[n] = 2^ceil(log2(max|W[n, :]| / 448))   (1.0 for an all-zero row),   q[n, :] = fp8(W[n, :] / scale[n]).
@@ -630,9 +638,25 @@ class LlamaEngine:
     # rows 1 / 2 / 3 / 4: bf16 2635 / 2910 / 2987 / 3067, fp8 1826 / 2156 / 2531 / 2986, mxfp4 1551 / 1876 / 2277 / 2872 =
     # 0.59 / 0.65 / 0.76 / 0.94 of the bf16 step: 6.4 % at 4 rows counts, so the range is every row count the kernels exist for.
     MXFP4_MAX_ROWS = 4
+    # lm_head_dtype="fp8" / "mxfp4" engines: decode graphs of up to this many rows stream the quantised head (csrc/lm_head_wq.hip, which
+    # exists for 1..4 rows), larger ones take the bf16 lm_head route on the dequantised head. The rule of FP8_MAX_ROWS: the largest row
+    # count at which the captured step with the quantised head beats the step with the bf16 head (same weight_dtype, same rows, same
+    # process) by >= 3 %, measured under weight_dtype="mxfp4", where the head's share of the step is largest; 0 when no row count does.
+    # Measured on MI355X, Qwen2.5-7B shapes at context 1536 (scripts/exp/lm_head_q_cost.py, profiles/lm_head_q_cost.txt: one engine per
+    # weight_dtype with its head switched, the configurations alternated in one process, 3 rounds of 96 replays, medians; rounds
+    # within 2 us), us per captured decode step by rows 1 / 2 / 3 / 4, head bf16 | fp8 | mxfp4 (ratios to the bf16 head):
+    #   weight_dtype mxfp4: 1536 / 1880 / 2274 / 2881 | 1447 / 1783 / 2201 / 2835 (0.942 / 0.948 / 0.968 / 0.984)
+    #                       | 1432 / 1769 / 2174 / 2810 (0.932 / 0.941 / 0.956 / 0.975)
+    #   weight_dtype fp8:   1830 / 2167 / 2541 / 3020 | 1744 / 2087 / 2467 / 2975 (0.953 / 0.963 / 0.971 / 0.985)
+    #                       | 1710 / 2055 / 2446 / 2951 (0.935 / 0.948 / 0.962 / 0.977)
+    #   weight_dtype bf16:  2646 / 2926 / 3006 / 3093 | 2564 / 2849 / 2938 / 3065 (0.969 / 0.974 / 0.977 / 0.991)
+    #                       | 2528 / 2817 / 2918 / 3043 (0.955 / 0.963 / 0.971 / 0.984)
+    # Under weight_dtype="mxfp4" both heads save >= 3 % up to 3 rows; 1.6 % (fp8) and 2.5 % (mxfp4) at 4 rows do not count.
+    LM_HEAD_FP8_MAX_ROWS = 3
+    LM_HEAD_MXFP4_MAX_ROWS = 3
 
     def __init__(self, cfg: LLMConfig, weights: dict, device="cuda:0", max_batch: int = 1, max_len: int = 4096,
-                 weight_dtype: str = "bf16"):
+                 weight_dtype: str = "bf16", lm_head_dtype: str = "bf16"):
         """weight_dtype="fp8": weight-only FP8 for the decode weight stream. w_qkv, w_o, w_gu and w_down of every layer are
         quantised per output row (`quantize_fp8_rows`: OCP e4m3 with a power-of-two scale; embeddings, lm_head, norms and biases
         stay bf16) and the layer's bf16 matrices are REPLACED by the dequantised W_eff, which bf16 holds exactly. The engine then
@@ -645,8 +669,22 @@ class LlamaEngine:
         steps of up to MXFP4_MAX_ROWS rows stream the nibbles (`*_q4`) and the scale bytes (`*_e4`), which the kernel applies inside
         the conversion. The format is coarse (11.8 % relative RMS weight error on N(0, 0.02^2) rows, FP8 2.6 %) and no text-quality
         claim is made for it.
-        The default "bf16" changes nothing: no tensor, no kernel, no graph key."""
+        The default "bf16" changes nothing: no tensor, no kernel, no graph key.
+        lm_head_dtype="fp8" / "mxfp4" (independent of weight_dtype, which leaves the head alone): the same construction on the
+        lm_head. `lm_head` becomes W_eff = dequantize(quantize(head)), a bf16 matrix of its own even when the configuration ties
+        the embeddings (`embed_w` keeps the checkpoint's values: the engine is a model with an untied, quantised head), and the
+        bytes live beside it: `lm_head_q8` / `lm_head_s8` (float8_e4m3fn [V, H], fp32 [V]) or `lm_head_q4` / `lm_head_e4` (uint8
+        [V, H / 2], [V, H / 32]). The fragment-major copy, the prefill's first-token lm_head and decode graphs of more than
+        LM_HEAD_FP8_MAX_ROWS / LM_HEAD_MXFP4_MAX_ROWS rows run on W_eff; decode steps of up to that many rows stream the bytes in the
+        lm_head launch (greedy, processed, sampling and beam branches alike). Graph keys do not change. The formats are as coarse
+        on the head as on the layers (module docstring of tests/test_llm_lm_head_q_gpu.py has the figures) and no text-quality claim
+        is made; the default "bf16" adds no tensor, no kernel and no graph key."""
         self.weight_dtype = resolve_weight_dtype(weight_dtype)
+        self.lm_head_dtype = resolve_lm_head_dtype(lm_head_dtype)
+        if self.lm_head_dtype == "mxfp4" and cfg.hidden % 32:
+            raise ValueError("lm_head_dtype='mxfp4' needs hidden to be a multiple of 32 (one E8M0 scale per block of 32 weights)")
+        if self.lm_head_dtype == "fp8" and cfg.hidden % 16:
+            raise ValueError("lm_head_dtype='fp8' needs hidden to be a multiple of 16 (16 weights per 16-byte load)")
         if self.weight_dtype == "mxfp4" and (cfg.hidden % 32 or cfg.inter % 32 or (cfg.n_q * cfg.head_dim) % 32):
             raise ValueError("weight_dtype='mxfp4' needs hidden, inter and n_q * head_dim to be multiples of 32 (one E8M0 scale per block of 32 weights)")
         if self.weight_dtype == "fp8" and (cfg.hidden % 16 or cfg.inter % 16 or (cfg.n_q * cfg.head_dim) % 16):
@@ -656,7 +694,9 @@ class LlamaEngine:
         dv = self.device
         g = lambda k: weights[k].to(device=dv, dtype=BF16).contiguous()
         self.embed_w = g("model.embed_tokens.weight")
-        self.lm_head = self.embed_w if (cfg.tie_embeddings or "lm_head.weight" not in weights) else g("lm_head.weight")
+        self._head_tied = bool(cfg.tie_embeddings or "lm_head.weight" not in weights)
+        self.lm_head = self.embed_w if self._head_tied else g("lm_head.weight")
+        self._quantize_head()
         self.norm = g("model.norm.weight")
         self.layers = []
         for l in range(cfg.layers):
@@ -695,9 +735,25 @@ class LlamaEngine:
             self.lm_head_fm = ops.repack_fm16(self.lm_head, self.norm)
         self._alloc()
 
+    def _quantize_head(self):
+        """lm_head_dtype="fp8" / "mxfp4": quantise the head's source -- the embedding matrix of a tied configuration, else the head
+        matrix itself, where both quantisers are fixed points in values -- and make `lm_head` its W_eff beside the bytes"""
+        if self.lm_head_dtype == "bf16":
+            return
+        src = self.embed_w if self._head_tied else self.lm_head
+        if self.lm_head_dtype == "fp8":
+            q, sc = quantize_fp8_rows(src)
+            self.lm_head = dequantize_fp8_rows(q, sc).contiguous()
+            self.lm_head_q8, self.lm_head_s8 = q.contiguous(), sc.contiguous()
+        else:
+            q, sc = quantize_mxfp4(src)
+            self.lm_head = dequantize_mxfp4(q, sc).contiguous()
+            self.lm_head_q4, self.lm_head_e4 = q.contiguous(), sc.contiguous()
+
     # ------------------------------------------------------------------ construction helpers
     @classmethod
-    def random_init(cls, cfg: LLMConfig, device="cuda:0", max_batch=1, max_len=4096, seed=0, std=0.02, weight_dtype="bf16"):
+    def random_init(cls, cfg: LLMConfig, device="cuda:0", max_batch=1, max_len=4096, seed=0, std=0.02, weight_dtype="bf16",
+                    lm_head_dtype="bf16"):
         """Random N(0, std^2) weights of the architecture's true shapes, created directly in HBM
         (init scheme of modeling_llama3.py:405-414). Used by bench.py: timing is weight-value independent."""
         gen = torch.Generator(device=device).manual_seed(seed)
@@ -722,20 +778,22 @@ class LlamaEngine:
             w[p + "mlp.down_proj.weight"] = r(cfg.hidden, cfg.inter)
             w[p + "input_layernorm.weight"] = one(cfg.hidden)
             w[p + "post_attention_layernorm.weight"] = one(cfg.hidden)
-        return cls(cfg, w, device, max_batch, max_len, weight_dtype=weight_dtype)
+        return cls(cfg, w, device, max_batch, max_len, weight_dtype=weight_dtype, lm_head_dtype=lm_head_dtype)
 
     @classmethod
-    def from_pretrained(cls, path: str, device="cuda:0", max_batch=1, max_len=4096, weight_dtype="bf16"):
+    def from_pretrained(cls, path: str, device="cuda:0", max_batch=1, max_len=4096, weight_dtype="bf16", lm_head_dtype="bf16"):
         """Load an HF checkpoint directory: config.json + model.safetensors(.index.json + shards) or pytorch_model.bin
         (spider_amd/checkpoint.py). From a Qwen2.5-Omni directory only `thinker.model.*` / `thinker.lm_head.*` are read.
-        weight_dtype="fp8" / "mxfp4" quantise the layer matrices at load (see the constructor)."""
+        weight_dtype="fp8" / "mxfp4" quantise the layer matrices at load, lm_head_dtype="fp8" / "mxfp4" the lm_head (see the
+        constructor)."""
         from .checkpoint import load_state_dict, read_config
 
         def keep(k: str):
             kk = k.replace("thinker.model.", "model.").replace("thinker.lm_head.", "lm_head.")
             return kk if kk.startswith(("model.", "lm_head.")) else None
         cfg = LLMConfig.from_hf_dict(read_config(path))
-        eng = cls(cfg, load_state_dict(path, keep=keep), device, max_batch, max_len, weight_dtype=weight_dtype)
+        eng = cls(cfg, load_state_dict(path, keep=keep), device, max_batch, max_len, weight_dtype=weight_dtype,
+                  lm_head_dtype=lm_head_dtype)
         eng.generation_config = read_generation_config(path)
         return eng
 
@@ -783,9 +841,13 @@ class LlamaEngine:
             if new_num_tokens > old:
                 out[old:] = (torch.randn(new_num_tokens - old, w.shape[1], generator=gen, device=w.device, dtype=torch.float32) * std).to(w.dtype)
             return out.contiguous()
-        tied = self.lm_head is self.embed_w
+        quant = self.lm_head_dtype != "bf16"    # a quantised head is a matrix of its own: the configuration says whether it is tied
+        tied = self._head_tied if quant else self.lm_head is self.embed_w
         self.embed_w = grow(self.embed_w)
-        self.lm_head = self.embed_w if tied else grow(self.lm_head)
+        if not tied:
+            self.lm_head = grow(self.lm_head)
+        elif not quant:
+            self.lm_head = self.embed_w     # (a tied quantised head is re-derived from embed_w by _vocab_changed)
         import dataclasses
         self.cfg = dataclasses.replace(c, vocab=new_num_tokens)     # (the config object may be shared with other engines)
         self._vocab_changed()
@@ -794,8 +856,10 @@ class LlamaEngine:
     def load_token_rows(self, first_row: int, embed_rows: Optional[torch.Tensor] = None, lm_head_rows: Optional[torch.Tensor] = None):
         """Overwrite rows [first_row, first_row + n) of the input embedding and / or the lm_head: the trained rows a Spider
         checkpoint stores for its signal tokens (the reference keeps `old_embed_tokens` / `old_lm_head` copies for exactly
-        this split, spider.py:165-173)."""
-        for w, rows, name in ((self.embed_w, embed_rows, "embed_rows"), (self.lm_head, lm_head_rows, "lm_head_rows")):
+        this split, spider.py:165-173). With a quantised head (lm_head_dtype) the rows land in the matrix a bf16 engine would
+        write -- the embedding matrix of a tied configuration, else the head -- and the head is quantised again from it."""
+        head = self.embed_w if (self.lm_head_dtype != "bf16" and self._head_tied) else self.lm_head
+        for w, rows, name in ((self.embed_w, embed_rows, "embed_rows"), (head, lm_head_rows, "lm_head_rows")):
             if rows is None:
                 continue
             if rows.ndim != 2 or rows.shape[1] != w.shape[1] or first_row < 0 or first_row + rows.shape[0] > w.shape[0]:
@@ -832,7 +896,9 @@ class LlamaEngine:
 
     def _vocab_changed(self):
         """the lm_head moved or changed: drop what was derived from it (fragment-major copy, captured decode graphs, lm_head
-        workspaces and logits buffers, all keyed in self._graphs)"""
+        workspaces and logits buffers, all keyed in self._graphs); a quantised head is quantised again from its source first
+        (rows nobody touched keep their W_eff values: both quantisers are fixed points in values)"""
+        self._quantize_head()
         if self.fm_batch:
             self.lm_head_fm = ops.repack_fm16(self.lm_head, self.norm)
         self._graphs = {}
@@ -874,7 +940,7 @@ class LlamaEngine:
         if hs is not None:
             hs[0].copy_(h)
         fm = self.fm_batch and B >= self.FM_MIN_BATCH
-        # FP8 engines: up to FP8_MAX_ROWS rows the four layer GEMVs stream the e4m3 bytes (the lm_head stays on its bf16 route)
+        # FP8 engines: up to FP8_MAX_ROWS rows the four layer GEMVs stream the e4m3 bytes (the lm_head follows lm_head_dtype: _lm_head_step)
         w8 = self.weight_dtype == "fp8" and B <= min(self.FP8_MAX_ROWS, ops.W8_MAX_ROWS)
         fuse_norm = not fm and B < 5      # the row-major GEMV folds the RMSNorm for up to 4 rows; the skinny MFMA GEMM (fm) carries it in its weights
         w8_fuse = w8 and ops.w8_norm_fits(B, c.hidden)     # (a hidden size beyond the kernel's LDS budget: RMSNorm in its own launch)
@@ -932,36 +998,15 @@ class LlamaEngine:
             if hs is not None:
                 hs[l + 1].copy_(h)
         if st.get("beam") is not None:      # beam search: the raw logits of the B * K rows go to the beam step instead of an arg-max
-            bm = st["beam"]
-            if fm:
-                ops.lm_head_argmax_fm(self.lm_head_fm, h, c.vocab, out_ids=bm["lm_ids"], ws=st["lm_ws"], logits=st["logits"],
-                                      norm_eps=c.eps)
-            else:
-                ops.lm_head_argmax(self.lm_head, h, norm_w=self.norm, eps=c.eps, out_ids=bm["lm_ids"], ws=st["lm_ws"],
-                                   logits=st["logits"])
+            self._lm_head_step(st, h, st["beam"]["lm_ids"], st["logits"], None, fm)
             self._beam_step(st)
             return
         proc = st.get("proc")      # logits processors in the arg-max epilogue (their parameters are read from the state's buffers)
         if st.get("sample") is not None:    # sampling: the raw logits go to the sampling step, which applies the processors itself
-            if fm:
-                ops.lm_head_argmax_fm(self.lm_head_fm, h, c.vocab, out_ids=st["sample"]["lm_ids"], ws=st["lm_ws"], logits=st["logits"],
-                                      norm_eps=c.eps)
-            else:
-                ops.lm_head_argmax(self.lm_head, h, norm_w=self.norm, eps=c.eps, out_ids=st["sample"]["lm_ids"], ws=st["lm_ws"],
-                                   logits=st["logits"])
+            self._lm_head_step(st, h, st["sample"]["lm_ids"], st["logits"], None, fm)
             self._sample_step(st)
-        elif proc is not None and fm:
-            ops.lm_head_argmax_fm_proc(self.lm_head_fm, h, c.vocab, proc, out_ids=st["next_ids"], ws=st["lm_ws"],
-                                       logits=st.get("logits"), norm_eps=c.eps)
-        elif proc is not None:
-            ops.lm_head_argmax_proc(self.lm_head, h, proc, norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"], ws=st["lm_ws"],
-                                    logits=st.get("logits"))
-        elif fm:
-            ops.lm_head_argmax_fm(self.lm_head_fm, h, c.vocab, out_ids=st["next_ids"], ws=st["lm_ws"], logits=st.get("logits"),
-                                  norm_eps=c.eps)
         else:
-            ops.lm_head_argmax(self.lm_head, h, norm_w=self.norm, eps=c.eps, out_ids=st["next_ids"], ws=st["lm_ws"],
-                               logits=st.get("logits"))
+            self._lm_head_step(st, h, st["next_ids"], st.get("logits"), proc, fm)
         if hs is not None:  # HF reports the normed state as the last hidden state (modeling_llama3.py:619-623)
             ops.rmsnorm(h, self.norm, c.eps, out=hs[c.layers])
         # advance the device-side cursors and append the token to the on-device history (index math only, one launch)
@@ -973,6 +1018,38 @@ class LlamaEngine:
                                     st["hist"], st["n_hist"])
         else:
             ops.decode_advance(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["hist"], st["n_hist"])
+
+    def _lm_head_step(self, st: dict, h: torch.Tensor, out_ids: torch.Tensor, logits: Optional[torch.Tensor], proc: Optional[dict],
+                      fm: bool):
+        """The lm_head launch of a decode step: final norm + lm_head + arg-max (through `proc` when given) of the residual stream h
+        into out_ids, raw logits into `logits` when given. Engines with a quantised head stream its bytes up to
+        LM_HEAD_FP8_MAX_ROWS / LM_HEAD_MXFP4_MAX_ROWS rows (csrc/lm_head_wq.hip); everything else is the bf16 route on `lm_head`:
+        fragment-major when `fm`, else row-major."""
+        c, B, ws = self.cfg, st["B"], st["lm_ws"]
+        if self.lm_head_dtype == "fp8" and B <= min(self.LM_HEAD_FP8_MAX_ROWS, ops.LM_HEAD_Q_MAX_ROWS):
+            fuse = ops.w8_norm_fits(B, c.hidden)    # (a hidden size beyond the kernel's LDS budget: RMSNorm in its own launch)
+            x, nw = (h, self.norm) if fuse else (ops.rmsnorm(h, self.norm, c.eps, out=st["xn"]), None)
+            if proc is not None:
+                ops.lm_head_argmax_proc_w8(self.lm_head_q8, self.lm_head_s8, x, proc, norm_w=nw, eps=c.eps, out_ids=out_ids, ws=ws,
+                                           logits=logits)
+            else:
+                ops.lm_head_argmax_w8(self.lm_head_q8, self.lm_head_s8, x, norm_w=nw, eps=c.eps, out_ids=out_ids, ws=ws, logits=logits)
+        elif self.lm_head_dtype == "mxfp4" and B <= min(self.LM_HEAD_MXFP4_MAX_ROWS, ops.LM_HEAD_Q_MAX_ROWS):
+            fuse = ops.w4_norm_fits(B, c.hidden)
+            x, nw = (h, self.norm) if fuse else (ops.rmsnorm(h, self.norm, c.eps, out=st["xn"]), None)
+            if proc is not None:
+                ops.lm_head_argmax_proc_w4(self.lm_head_q4, self.lm_head_e4, x, proc, norm_w=nw, eps=c.eps, out_ids=out_ids, ws=ws,
+                                           logits=logits)
+            else:
+                ops.lm_head_argmax_w4(self.lm_head_q4, self.lm_head_e4, x, norm_w=nw, eps=c.eps, out_ids=out_ids, ws=ws, logits=logits)
+        elif proc is not None and fm:
+            ops.lm_head_argmax_fm_proc(self.lm_head_fm, h, c.vocab, proc, out_ids=out_ids, ws=ws, logits=logits, norm_eps=c.eps)
+        elif proc is not None:
+            ops.lm_head_argmax_proc(self.lm_head, h, proc, norm_w=self.norm, eps=c.eps, out_ids=out_ids, ws=ws, logits=logits)
+        elif fm:
+            ops.lm_head_argmax_fm(self.lm_head_fm, h, c.vocab, out_ids=out_ids, ws=ws, logits=logits, norm_eps=c.eps)
+        else:
+            ops.lm_head_argmax(self.lm_head, h, norm_w=self.norm, eps=c.eps, out_ids=out_ids, ws=ws, logits=logits)
 
     def _sample_step(self, st: dict):
         """Behind the raw-logits lm_head of a sampling step (graph-capturable, no host sync): st["next_ids"] = one draw per row from

@@ -534,6 +534,80 @@ def lm_head_argmax_fm_proc(Wfm, x, V, proc: dict, out_ids=None, logits=None, ws=
     return out_ids
 
 
+LM_HEAD_Q_MAX_ROWS = 4         # rows the weight-only lm_head kernels exist for (csrc/lm_head_wq.hip)
+
+
+def _lm_head_q_bufs(name, x, B, V, K, norm_w, out_ids, logits, ws):
+    """rows, norm, ids, logits and workspaces of the lm_head_argmax*_w8 / _w4 calls, checked and allocated where missing"""
+    if not 1 <= B <= LM_HEAD_Q_MAX_ROWS:
+        raise ValueError(f"{name}: {B} rows of x, the weight-only lm_head kernels exist for 1..{LM_HEAD_Q_MAX_ROWS}")
+    if norm_w is not None:
+        _chk(norm_w, BF16, "norm_w")
+        if norm_w.numel() != K:
+            raise ValueError(f"{name}: norm_w has {norm_w.numel()} elements, K is {K}")
+    npart = lm_head_nparts(V)
+    if ws is None:
+        ws = (torch.empty(B * npart, dtype=torch.float32, device=x.device), torch.empty(B * npart, dtype=torch.int32, device=x.device))
+    _chk(ws[0], torch.float32, "ws[0]"); _chk(ws[1], torch.int32, "ws[1]")
+    if ws[0].numel() < B * npart or ws[1].numel() < B * npart:
+        raise ValueError(f"{name}: the workspaces need {B * npart} entries each")
+    if logits is not None:
+        _chk(logits, BF16, "logits")
+        if logits.numel() != B * V:
+            raise ValueError(f"{name}: logits has {logits.numel()} elements, expected [{B}, {V}]")
+    if out_ids is None:
+        out_ids = torch.empty(B, dtype=torch.int32, device=x.device)
+    _chk(out_ids, torch.int32, "out_ids")
+    if out_ids.numel() < B:
+        raise ValueError(f"{name}: out_ids needs {B} entries")
+    return out_ids, ws
+
+
+def lm_head_argmax_w8(q, scale, x, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=None):
+    """`lm_head_argmax` on a weight-only FP8 head (llm.quantize_fp8_rows): q [V, K] float8_e4m3fn, scale [V] fp32; the fp32 sum is
+    scaled once after the reduction. 1 <= B <= 4, K % 16 == 0; the fused norm needs w8_norm_fits(B, K)."""
+    K, B = _chk_w8(q, scale, x, "q")
+    if K % 16:
+        raise ValueError(f"q: K = {K} has to be a multiple of 16 (16 e4m3 weights per 16-byte load)")
+    out_ids, ws = _lm_head_q_bufs("lm_head_argmax_w8", x, B, q.shape[0], K, norm_w, out_ids, logits, ws)
+    _lib.call("spider_lm_head_argmax_w8", _p(q), _p(scale), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
+              _p(ws[0]), _p(ws[1]), B, q.shape[0], K, _stream())
+    return out_ids
+
+
+def lm_head_argmax_proc_w8(q, scale, x, proc: dict, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=None):
+    """lm_head_argmax_w8 with the logits processors of lm_head_argmax_proc in the arg-max epilogue; `logits` stay raw."""
+    K, B = _chk_w8(q, scale, x, "q")
+    if K % 16:
+        raise ValueError(f"q: K = {K} has to be a multiple of 16 (16 e4m3 weights per 16-byte load)")
+    V = q.shape[0]
+    out_ids, ws = _lm_head_q_bufs("lm_head_argmax_proc_w8", x, B, V, K, norm_w, out_ids, logits, ws)
+    _lib.call("spider_lm_head_argmax_proc_w8", _p(q), _p(scale), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
+              _p(ws[0]), _p(ws[1]), *_proc_args(proc, B, V), B, V, K, _stream())
+    return out_ids
+
+
+def lm_head_argmax_w4(blocks, scales, x, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=None):
+    """`lm_head_argmax` on a weight-only MXFP4 head (llm.quantize_mxfp4): blocks [V, K / 2] uint8, scales [V, K / 32] uint8 (E8M0,
+    bytes 1..254), the block scale applied inside the conversion. 1 <= B <= 4, K % 32 == 0; the fused norm needs
+    w4_norm_fits(B, K)."""
+    K, B = _chk_w4(blocks, scales, x, "blocks")
+    out_ids, ws = _lm_head_q_bufs("lm_head_argmax_w4", x, B, blocks.shape[0], K, norm_w, out_ids, logits, ws)
+    _lib.call("spider_lm_head_argmax_w4", _p(blocks), _p(scales), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
+              _p(ws[0]), _p(ws[1]), B, blocks.shape[0], K, _stream())
+    return out_ids
+
+
+def lm_head_argmax_proc_w4(blocks, scales, x, proc: dict, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=None):
+    """lm_head_argmax_w4 with the logits processors of lm_head_argmax_proc in the arg-max epilogue; `logits` stay raw."""
+    K, B = _chk_w4(blocks, scales, x, "blocks")
+    V = blocks.shape[0]
+    out_ids, ws = _lm_head_q_bufs("lm_head_argmax_proc_w4", x, B, V, K, norm_w, out_ids, logits, ws)
+    _lib.call("spider_lm_head_argmax_proc_w4", _p(blocks), _p(scales), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
+              _p(ws[0]), _p(ws[1]), *_proc_args(proc, B, V), B, V, K, _stream())
+    return out_ids
+
+
 def decode_advance_seen(next_ids, cur_ids, pos, slot, kv_end, seen, V, hist=None, n_hist=None):
     """decode_advance, and bit next_ids[b] of seen [B, ceil(V/32)] is set (the processed greedy path's token set)."""
     for t, n in ((next_ids, "next_ids"), (cur_ids, "cur_ids"), (pos, "pos"), (slot, "slot"), (kv_end, "kv_end"), (seen, "seen")):

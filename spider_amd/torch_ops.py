@@ -274,6 +274,66 @@ def _(blocks_gate_up, scales, x, norm_w=None, eps=1e-6):
     return x.new_empty(x.numel() // (2 * blocks_gate_up.shape[1]), blocks_gate_up.shape[0] // 2)
 
 
+# ------------------------------------------------------------------------------------------ weight-only FP8 / MXFP4 lm_head
+def _as_fp8(q: torch.Tensor) -> torch.Tensor:
+    return q.view(ops.FP8) if q.dtype == torch.uint8 else q
+
+
+@_op("lm_head_argmax_w8")
+def lm_head_argmax_w8(h: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, norm_w: Optional[torch.Tensor] = None,
+                      eps: float = 1e-6) -> torch.Tensor:
+    """final RMSNorm (optional) + lm_head + greedy argmax on a weight-only FP8 head: q [V, K] float8_e4m3fn (or the same bytes as
+    uint8), scale [V] fp32; ties -> lowest id; h [B <= 4, K] -> int32 [B]"""
+    return ops.lm_head_argmax_w8(_as_fp8(q), scale, h.contiguous(), norm_w=norm_w, eps=eps)
+
+
+@lm_head_argmax_w8.register_fake
+def _(h, q, scale, norm_w=None, eps=1e-6):
+    return h.new_empty(h.numel() // q.shape[1], dtype=torch.int32)
+
+
+@_op("lm_head_argmax_proc_w8")
+def lm_head_argmax_proc_w8(h: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, seen: torch.Tensor, ban: torch.Tensor,
+                           penalty: torch.Tensor, min_new: torch.Tensor, eos_ids: torch.Tensor, n_eos: torch.Tensor,
+                           n_hist: torch.Tensor, norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6) -> torch.Tensor:
+    """lm_head_argmax_w8 with the logits processors in the arg-max epilogue: repetition penalty on the ids of `seen`, -inf on the
+    ids of `ban` and on the EOS ids while n_hist < min_new (buffers of ops.lm_head_argmax_proc)"""
+    proc = dict(seen=seen, ban=ban, penalty=penalty, min_new=min_new, eos_ids=eos_ids, n_eos=n_eos, n_hist=n_hist)
+    return ops.lm_head_argmax_proc_w8(_as_fp8(q), scale, h.contiguous(), proc, norm_w=norm_w, eps=eps)
+
+
+@lm_head_argmax_proc_w8.register_fake
+def _(h, q, scale, seen, ban, penalty, min_new, eos_ids, n_eos, n_hist, norm_w=None, eps=1e-6):
+    return h.new_empty(h.numel() // q.shape[1], dtype=torch.int32)
+
+
+@_op("lm_head_argmax_w4")
+def lm_head_argmax_w4(h: torch.Tensor, blocks: torch.Tensor, scales: torch.Tensor, norm_w: Optional[torch.Tensor] = None,
+                      eps: float = 1e-6) -> torch.Tensor:
+    """final RMSNorm (optional) + lm_head + greedy argmax on a weight-only MXFP4 head: blocks [V, K / 2] uint8, scales [V, K / 32]
+    uint8 (E8M0); ties -> lowest id; h [B <= 4, K] -> int32 [B]"""
+    return ops.lm_head_argmax_w4(blocks, scales, h.contiguous(), norm_w=norm_w, eps=eps)
+
+
+@lm_head_argmax_w4.register_fake
+def _(h, blocks, scales, norm_w=None, eps=1e-6):
+    return h.new_empty(h.numel() // (2 * blocks.shape[1]), dtype=torch.int32)
+
+
+@_op("lm_head_argmax_proc_w4")
+def lm_head_argmax_proc_w4(h: torch.Tensor, blocks: torch.Tensor, scales: torch.Tensor, seen: torch.Tensor, ban: torch.Tensor,
+                           penalty: torch.Tensor, min_new: torch.Tensor, eos_ids: torch.Tensor, n_eos: torch.Tensor,
+                           n_hist: torch.Tensor, norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6) -> torch.Tensor:
+    """lm_head_argmax_w4 with the logits processors of lm_head_argmax_proc_w8"""
+    proc = dict(seen=seen, ban=ban, penalty=penalty, min_new=min_new, eos_ids=eos_ids, n_eos=n_eos, n_hist=n_hist)
+    return ops.lm_head_argmax_proc_w4(blocks, scales, h.contiguous(), proc, norm_w=norm_w, eps=eps)
+
+
+@lm_head_argmax_proc_w4.register_fake
+def _(h, blocks, scales, seen, ban, penalty, min_new, eos_ids, n_eos, n_hist, norm_w=None, eps=1e-6):
+    return h.new_empty(h.numel() // (2 * blocks.shape[1]), dtype=torch.int32)
+
+
 # ------------------------------------------------------------------------------------------ safety checker around the CLIP ViT
 @_op("clip_preprocess")
 def clip_preprocess(images: torch.Tensor, xbounds: torch.Tensor, xtaps: torch.Tensor, ybounds: torch.Tensor, ytaps: torch.Tensor,
@@ -354,13 +414,14 @@ def _(packed_u8, desc, tabs, lut, rows, patch, merge, temporal, tmp_bytes, max_h
     return packed_u8.new_empty(rows, 3 * temporal * patch * patch, dtype=torch.float32 if f32 else BF16)
 
 
-# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 and MXFP4 GEMVs, the safety-checker ops and the audio
-# and image feature ops above are listed apart
+# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 and MXFP4 GEMVs and lm_heads, the safety-checker
+# ops and the audio and image feature ops above are listed apart
 SAFETY_OP_NAMES = ("clip_preprocess", "safety_decide", "image_blackout_")
 AUDIO_OP_NAMES = ("logmel",)
 IMAGE_OP_NAMES = ("qwen_image_patches",)
 W8_OP_NAMES = ("gemv_w8", "gemv_swiglu_w8")
 W4_OP_NAMES = ("gemv_w4", "gemv_swiglu_w4")
+LM_HEAD_Q_OP_NAMES = ("lm_head_argmax_w8", "lm_head_argmax_proc_w8", "lm_head_argmax_w4", "lm_head_argmax_proc_w4")
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
             "conv2d_nhwc", "attn_self", "attn_cross_kv77", "attn_consistent", "geglu", "cfg_step")
