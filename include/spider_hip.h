@@ -76,6 +76,23 @@ int spider_gemv_w4(const void* blocks, const void* scales, const void* x, void* 
 int spider_gemv_swiglu_w4(const void* blocks_gate_up, const void* scales, const void* x, void* out, const void* norm_w, float eps,
                           int B, int I, int K, void* stream);
 
+/* Fragment-major weight-only forms for 1 <= B <= 16 rows (csrc/gemv_qfm.hip): the weight decode sits in front of the MFMA of
+ * spider_gemv_fm_bf16, the activation rows are its B operand. No fused RMSNorm: x is used as it is.
+ *   _w4: qfm [ceil(N/16), K/128, 64, 16] bytes, efm [ceil(N/16), K/128, 16, 4] bytes, K % 128 == 0. In piece (rg, kb) byte 4 sx + j of
+ *        lane 16 g + r is blocks[16 rg + r][(128 kb + 32 sx + 8 g) / 2 + j] and efm byte (r, sx) is scales[16 rg + r][4 kb + sx], in
+ *        the terms of spider_gemv_w4; padding rows hold nibble code 0 and scale byte 127.
+ *   _w8: qfm [ceil(N/16), K/64, 64, 16] bytes, K % 64 == 0: byte 8 sx + e of lane 16 g + r is Wq[16 rg + r][64 kb + 32 sx + 8 g + e];
+ *        scale [N] fp32 as in spider_gemv_w8, applied once to the fp32 sum.
+ * Epilogues as spider_gemv_w4 / _w8: (+bias) -> bf16 -> (+res -> bf16); the swiglu forms take the copy of [gate rows | up rows]
+ * (I % 16 == 0; scale [2 I]) and give bf16(bf16(silu(bf16(g))) * bf16(u)). K, B outside 1..16, I % 16 and null pointers are refused
+ * (-1) before any launch. */
+int spider_gemv_fm_w4(const void* qfm, const void* efm, const void* x, void* out, const void* bias, const void* res, int B, int N,
+                      int K, void* stream);
+int spider_gemv_swiglu_fm_w4(const void* qfm_gate_up, const void* efm, const void* x, void* out, int B, int I, int K, void* stream);
+int spider_gemv_fm_w8(const void* qfm, const float* scale, const void* x, void* out, const void* bias, const void* res, int B, int N,
+                      int K, void* stream);
+int spider_gemv_swiglu_fm_w8(const void* qfm_gate_up, const float* scale, const void* x, void* out, int B, int I, int K, void* stream);
+
 /* final norm + lm_head + greedy argmax (modeling_llama3.py:619,870-871; HF greedy loop driven from
  * spider.py:1492-1508). logits (bf16 [B,V]) optional. ws_val/ws_idx: B*spider_lm_head_nparts(V) floats/ints. */
 int spider_lm_head_nparts(int V);

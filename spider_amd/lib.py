@@ -36,6 +36,10 @@ SIGNATURES = {
     "spider_gemv_swiglu_w8": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
     "spider_gemv_w4": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
     "spider_gemv_swiglu_w4": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
+    "spider_gemv_fm_w4": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "spider_gemv_swiglu_fm_w4": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "spider_gemv_fm_w8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "spider_gemv_swiglu_fm_w8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "spider_lm_head_nparts": (_i, [_i]),
     "spider_decode_advance_i32": (_i, [_vp] * 7 + [_i, _i, _vp]),
     "spider_lm_head_argmax_bf16": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -654,9 +654,19 @@ class LlamaEngine:
     # Under weight_dtype="mxfp4" both heads save >= 3 % up to 3 rows; 1.6 % (fp8) and 2.5 % (mxfp4) at 4 rows do not count.
     LM_HEAD_FP8_MAX_ROWS = 3
     LM_HEAD_MXFP4_MAX_ROWS = 3
+    # batched_weight_stream=True engines: decode graphs of more rows than FP8_MAX_ROWS / MXFP4_MAX_ROWS, up to this many, stream the
+    # quantised bytes in fragment-major order through the MFMA kernels of csrc/gemv_qfm.hip (which exist for 1..16 rows); larger ones take
+    # the bf16 fragment-major route on W_eff. The rule of FP8_MAX_ROWS: the largest row count <= DECODE_ROWS up to which EVERY row count
+    # above the row-major range beats the bf16 fragment-major step of the same row count, in the same process, by >= 3 %; 0 when none does.
+    # Measured on MI355X, Qwen2.5-7B shapes at context 1536, max_batch 8 (scripts/exp/qfm_decode_cost.py, profiles/qfm_decode_cost.txt:
+    # the three engines alternated in one process, 3 rounds of 96 replays, medians; rounds within 2 us), us per captured decode step by
+    # rows 4 / 5 / 6 / 8: bf16 3090 / 3145 / 3210 / 3340, fp8 2515 / 2571 / 2622 / 2758 = 0.814 / 0.817 / 0.817 / 0.826 of it, mxfp4
+    # (2878 row-major at 4 rows) 2325 / 2387 / 2543 = 0.739 / 0.743 / 0.762 of it at 5 / 6 / 8. 7 rows were not measured.
+    FP8_FM_MAX_ROWS = 8
+    MXFP4_FM_MAX_ROWS = 8
 
     def __init__(self, cfg: LLMConfig, weights: dict, device="cuda:0", max_batch: int = 1, max_len: int = 4096,
-                 weight_dtype: str = "bf16", lm_head_dtype: str = "bf16"):
+                 weight_dtype: str = "bf16", lm_head_dtype: str = "bf16", batched_weight_stream: bool = False):
         """weight_dtype="fp8": weight-only FP8 for the decode weight stream. w_qkv, w_o, w_gu and w_down of every layer are
         quantised per output row (`quantize_fp8_rows`: OCP e4m3 with a power-of-two scale; embeddings, lm_head, norms and biases
         stay bf16) and the layer's bf16 matrices are REPLACED by the dequantised W_eff, which bf16 holds exactly. The engine then
@@ -678,9 +688,27 @@ class LlamaEngine:
         LM_HEAD_FP8_MAX_ROWS / LM_HEAD_MXFP4_MAX_ROWS rows run on W_eff; decode steps of up to that many rows stream the bytes in the
         lm_head launch (greedy, processed, sampling and beam branches alike). Graph keys do not change. The formats are as coarse
         on the head as on the layers (module docstring of tests/test_llm_lm_head_q_gpu.py has the figures) and no text-quality claim
-        is made; the default "bf16" adds no tensor, no kernel and no graph key."""
+        is made; the default "bf16" adds no tensor, no kernel and no graph key.
+        batched_weight_stream=True (needs weight_dtype "fp8" / "mxfp4" and max_batch >= 5): decode steps of more rows than the
+        row-major kernels serve, up to FP8_FM_MAX_ROWS / MXFP4_FM_MAX_ROWS, stream the quantised bytes too, through the fragment-major
+        MFMA kernels of csrc/gemv_qfm.hip. Every layer gets one more quantised copy of its four matrices, repacked from the bytes the
+        engine already holds (`*_q8fm`, or `*_q4fm` / `*_e4fm`; ops.repack_fm_w8 / repack_fm_w4), and those steps run rmsnorm ->
+        gemv_fm_w* (qkv, bias) -> attention -> gemv_fm_w* (o, res) -> rmsnorm -> gemv_swiglu_fm_w* -> gemv_fm_w* (down, res): the same
+        function of W_eff as the bf16 fragment-major route, in another summation order and with the RMSNorm in a launch of its own
+        instead of folded into the weights. The lm_head is not touched. Graph keys do not change; the default False adds no tensor
+        and changes no step."""
         self.weight_dtype = resolve_weight_dtype(weight_dtype)
         self.lm_head_dtype = resolve_lm_head_dtype(lm_head_dtype)
+        self.batched_weight_stream = bool(batched_weight_stream)
+        if self.batched_weight_stream:
+            if self.weight_dtype == "bf16":
+                raise ValueError("batched_weight_stream=True needs weight_dtype 'fp8' or 'mxfp4' (a bf16 engine has no quantised bytes to stream)")
+            if max_batch < 5:
+                raise ValueError("batched_weight_stream=True needs max_batch >= 5 (up to 4 rows the row-major kernels stream the bytes)")
+            m = 128 if self.weight_dtype == "mxfp4" else 64
+            if cfg.hidden % m or cfg.inter % m or (cfg.n_q * cfg.head_dim) % m:
+                raise ValueError(f"batched_weight_stream=True with weight_dtype={self.weight_dtype!r} needs hidden, inter and n_q * head_dim "
+                                 f"to be multiples of {m} (one fragment-major piece is 16 rows x {m} weights)")
         if self.lm_head_dtype == "mxfp4" and cfg.hidden % 32:
             raise ValueError("lm_head_dtype='mxfp4' needs hidden to be a multiple of 32 (one E8M0 scale per block of 32 weights)")
         if self.lm_head_dtype == "fp8" and cfg.hidden % 16:
@@ -733,6 +761,13 @@ class LlamaEngine:
                 lw["w_o_fm"] = ops.repack_fm16(lw["w_o"])
                 lw["w_down_fm"] = ops.repack_fm16(lw["w_down"])
             self.lm_head_fm = ops.repack_fm16(self.lm_head, self.norm)
+        if self.batched_weight_stream:      # the third encoding of W_eff: the engine's own bytes in fragment-major order
+            for lw in self.layers:
+                for k in ("w_qkv", "w_o", "w_gu", "w_down"):
+                    if self.weight_dtype == "fp8":
+                        lw[k + "_q8fm"] = ops.repack_fm_w8(lw[k + "_q8"])
+                    else:
+                        lw[k + "_q4fm"], lw[k + "_e4fm"] = ops.repack_fm_w4(lw[k + "_q4"], lw[k + "_e4"])
         self._alloc()
 
     def _quantize_head(self):
@@ -753,7 +788,7 @@ class LlamaEngine:
     # ------------------------------------------------------------------ construction helpers
     @classmethod
     def random_init(cls, cfg: LLMConfig, device="cuda:0", max_batch=1, max_len=4096, seed=0, std=0.02, weight_dtype="bf16",
-                    lm_head_dtype="bf16"):
+                    lm_head_dtype="bf16", batched_weight_stream=False):
         """Random N(0, std^2) weights of the architecture's true shapes, created directly in HBM
         (init scheme of modeling_llama3.py:405-414). Used by bench.py: timing is weight-value independent."""
         gen = torch.Generator(device=device).manual_seed(seed)
@@ -778,14 +813,16 @@ class LlamaEngine:
             w[p + "mlp.down_proj.weight"] = r(cfg.hidden, cfg.inter)
             w[p + "input_layernorm.weight"] = one(cfg.hidden)
             w[p + "post_attention_layernorm.weight"] = one(cfg.hidden)
-        return cls(cfg, w, device, max_batch, max_len, weight_dtype=weight_dtype, lm_head_dtype=lm_head_dtype)
+        return cls(cfg, w, device, max_batch, max_len, weight_dtype=weight_dtype, lm_head_dtype=lm_head_dtype,
+                   batched_weight_stream=batched_weight_stream)
 
     @classmethod
-    def from_pretrained(cls, path: str, device="cuda:0", max_batch=1, max_len=4096, weight_dtype="bf16", lm_head_dtype="bf16"):
+    def from_pretrained(cls, path: str, device="cuda:0", max_batch=1, max_len=4096, weight_dtype="bf16", lm_head_dtype="bf16",
+                        batched_weight_stream=False):
         """Load an HF checkpoint directory: config.json + model.safetensors(.index.json + shards) or pytorch_model.bin
         (spider_amd/checkpoint.py). From a Qwen2.5-Omni directory only `thinker.model.*` / `thinker.lm_head.*` are read.
         weight_dtype="fp8" / "mxfp4" quantise the layer matrices at load, lm_head_dtype="fp8" / "mxfp4" the lm_head (see the
-        constructor)."""
+        constructor); batched_weight_stream=True adds the fragment-major quantised copies for decode graphs of 5..8 rows."""
         from .checkpoint import load_state_dict, read_config
 
         def keep(k: str):
@@ -793,7 +830,7 @@ class LlamaEngine:
             return kk if kk.startswith(("model.", "lm_head.")) else None
         cfg = LLMConfig.from_hf_dict(read_config(path))
         eng = cls(cfg, load_state_dict(path, keep=keep), device, max_batch, max_len, weight_dtype=weight_dtype,
-                  lm_head_dtype=lm_head_dtype)
+                  lm_head_dtype=lm_head_dtype, batched_weight_stream=batched_weight_stream)
         eng.generation_config = read_generation_config(path)
         return eng
 
@@ -947,8 +984,17 @@ class LlamaEngine:
         # MXFP4 engines: the same four GEMVs on the e2m1 bytes and their block scales, up to MXFP4_MAX_ROWS rows
         w4 = self.weight_dtype == "mxfp4" and B <= min(self.MXFP4_MAX_ROWS, ops.W4_MAX_ROWS)
         w4_fuse = w4 and ops.w4_norm_fits(B, c.hidden)
+        # batched_weight_stream engines: above those ranges, up to *_FM_MAX_ROWS rows, the same bytes in fragment-major order (csrc/gemv_qfm.hip)
+        q8fm = self.batched_weight_stream and self.weight_dtype == "fp8" and not w8 and B <= min(self.FP8_FM_MAX_ROWS, ops.QFM_MAX_ROWS)
+        q4fm = self.batched_weight_stream and self.weight_dtype == "mxfp4" and not w4 and B <= min(self.MXFP4_FM_MAX_ROWS, ops.QFM_MAX_ROWS)
         for l, lw in enumerate(self.layers):
-            if w8 and w8_fuse:
+            if q8fm:
+                ops.gemv_fm_w8(lw["w_qkv_q8fm"], lw["w_qkv_s8"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), lw["w_qkv"].shape[0],
+                               bias=lw["b_qkv"], out=st["qkv"])
+            elif q4fm:
+                ops.gemv_fm_w4(lw["w_qkv_q4fm"], lw["w_qkv_e4fm"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), lw["w_qkv"].shape[0],
+                               bias=lw["b_qkv"], out=st["qkv"])
+            elif w8 and w8_fuse:
                 ops.gemv_w8(lw["w_qkv_q8"], lw["w_qkv_s8"], h, bias=lw["b_qkv"], norm_w=lw["ln1"], eps=c.eps, out=st["qkv"])
             elif w8:
                 ops.gemv_w8(lw["w_qkv_q8"], lw["w_qkv_s8"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), bias=lw["b_qkv"], out=st["qkv"])
@@ -970,7 +1016,15 @@ class LlamaEngine:
                                    B, 1, c.n_q, c.n_kv, c.head_dim)
                 ops.attn_decode(st["q"], k_cache[l], v_cache[l], st["kv_end"], kv_beg=st["kv_beg"],
                                 nsplit=st["nsplit"], ws=st["attn_ws"], out=st["attn"])
-            if w8:
+            if q8fm:
+                h1 = ops.gemv_fm_w8(lw["w_o_q8fm"], lw["w_o_s8"], st["attn"], c.hidden, res=h, out=st["h1"])
+                ops.gemv_swiglu_fm_w8(lw["w_gu_q8fm"], lw["w_gu_s8"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
+                h = ops.gemv_fm_w8(lw["w_down_q8fm"], lw["w_down_s8"], st["act"], c.hidden, res=h1, out=st["h2"][l & 1])
+            elif q4fm:
+                h1 = ops.gemv_fm_w4(lw["w_o_q4fm"], lw["w_o_e4fm"], st["attn"], c.hidden, res=h, out=st["h1"])
+                ops.gemv_swiglu_fm_w4(lw["w_gu_q4fm"], lw["w_gu_e4fm"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
+                h = ops.gemv_fm_w4(lw["w_down_q4fm"], lw["w_down_e4fm"], st["act"], c.hidden, res=h1, out=st["h2"][l & 1])
+            elif w8:
                 h1 = ops.gemv_w8(lw["w_o_q8"], lw["w_o_s8"], st["attn"], res=h, out=st["h1"])
                 if w8_fuse:
                     ops.gemv_swiglu_w8(lw["w_gu_q8"], lw["w_gu_s8"], h1, norm_w=lw["ln2"], eps=c.eps, out=st["act"])

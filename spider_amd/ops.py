@@ -441,6 +441,141 @@ def gemv_swiglu_fm(Wfm_gate_up, x, out=None, norm_eps=None):
     return out
 
 
+QFM_MAX_ROWS = 16              # rows the fragment-major weight-only GEMVs exist for (one 16-wide MFMA tile)
+
+
+def _pad_rows(t: torch.Tensor, rows: int, fill: int) -> torch.Tensor:
+    if t.shape[0] == rows:
+        return t
+    return torch.cat([t, torch.full((rows - t.shape[0],) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)], 0)
+
+
+def repack_fm_w4(blocks: torch.Tensor, scales: torch.Tensor):
+    """MXFP4 weights in the public layout (blocks [N, K / 2] uint8, scales [N, K / 32] uint8; K % 128 == 0) -> the fragment-major
+    copies (qfm [NG, K / 128, 64, 16], efm [NG, K / 128, 16, 4]) of the *_fm_w4 kernels, NG = ceil(N / 16). In piece (rg, kb) byte
+    4 sx + j of lane 16 g + r is blocks[16 rg + r, (128 kb + 32 sx + 8 g) / 2 + j] -- dword sx of a lane holds
+    W[16 rg + r][128 kb + 32 sx + 8 g .. + 7], its A fragment of MFMA sub-step sx -- and efm byte (r, sx) is scales[16 rg + r, 4 kb + sx].
+    Rows are padded to a multiple of 16 with nibble code 0 and scale byte 127. Pure data movement, on whichever device the bytes are."""
+    if blocks.dtype != torch.uint8 or scales.dtype != torch.uint8 or blocks.dim() != 2 or scales.dim() != 2:
+        raise ValueError("repack_fm_w4: expected uint8 blocks [N, K / 2] and scales [N, K / 32]")
+    N, K = blocks.shape[0], blocks.shape[1] * 2
+    if K % 128 or N < 1 or tuple(scales.shape) != (N, K // 32):
+        raise ValueError(f"repack_fm_w4: K must be a multiple of 128 with scales [N, K / 32], got blocks {tuple(blocks.shape)} and "
+                         f"scales {tuple(scales.shape)}")
+    NG = (N + 15) // 16
+    b, s = _pad_rows(blocks, NG * 16, 0), _pad_rows(scales, NG * 16, 127)
+    # [rg, r, kb, sx, g, j] -> [rg, kb, g, r, sx, j];  [rg, r, kb, sx] -> [rg, kb, r, sx]
+    qfm = b.view(NG, 16, K // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5).contiguous().view(NG, K // 128, 64, 16)
+    efm = s.view(NG, 16, K // 128, 4).permute(0, 2, 1, 3).contiguous()
+    return qfm, efm
+
+
+def unpack_fm_w4(qfm: torch.Tensor, efm: torch.Tensor, N: int):
+    """the exact inverse of repack_fm_w4: (blocks [N, K / 2], scales [N, K / 32])"""
+    NG, KB = qfm.shape[0], qfm.shape[1]
+    if tuple(qfm.shape[2:]) != (64, 16) or tuple(efm.shape) != (NG, KB, 16, 4) or NG != (N + 15) // 16:
+        raise ValueError(f"unpack_fm_w4: qfm {tuple(qfm.shape)} / efm {tuple(efm.shape)} are no fragment-major copy of {N} rows")
+    b = qfm.view(NG, KB, 4, 16, 4, 4).permute(0, 3, 1, 4, 2, 5).contiguous().view(NG * 16, KB * 64)
+    s = efm.permute(0, 2, 1, 3).contiguous().view(NG * 16, KB * 4)
+    return b[:N].contiguous(), s[:N].contiguous()
+
+
+def repack_fm_w8(q: torch.Tensor) -> torch.Tensor:
+    """FP8 weights q [N, K] float8_e4m3fn (K % 64 == 0) -> the fragment-major copy qfm uint8 [NG, K / 64, 64, 16] of the *_fm_w8
+    kernels: in piece (rg, kb) byte 8 sx + e of lane 16 g + r is q[16 rg + r, 64 kb + 32 sx + 8 g + e]. Rows are padded to a multiple
+    of 16 with zero bytes; the per-row scale of llm.quantize_fp8_rows is used as it is."""
+    if q.dtype != FP8 or q.dim() != 2:
+        raise ValueError("repack_fm_w8: expected a float8_e4m3fn weight [N, K]")
+    N, K = q.shape
+    if K % 64 or N < 1:
+        raise ValueError(f"repack_fm_w8: K must be a multiple of 64, got {tuple(q.shape)}")
+    NG = (N + 15) // 16
+    b = _pad_rows(q.contiguous().view(torch.uint8), NG * 16, 0)
+    # [rg, r, kb, sx, g, e] -> [rg, kb, g, r, sx, e]
+    return b.view(NG, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous().view(NG, K // 64, 64, 16)
+
+
+def unpack_fm_w8(qfm: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """the exact inverse of repack_fm_w8: q [N, K] float8_e4m3fn"""
+    NG = (N + 15) // 16
+    if K % 64 or tuple(qfm.shape) != (NG, K // 64, 64, 16):
+        raise ValueError(f"unpack_fm_w8: qfm {tuple(qfm.shape)} is no fragment-major copy of [{N}, {K}]")
+    b = qfm.view(NG, K // 64, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5).contiguous().view(NG * 16, K)
+    return b[:N].contiguous().view(FP8)
+
+
+def _chk_qfm(qfm, sc, x, rows, name, fmt):
+    """shapes of a fragment-major weight-only call: -> (K, B). rows = weight rows of the copy (N, or 2 I); fmt 4 / 8"""
+    _chk(qfm, torch.uint8, name); _chk(x, BF16, "x")
+    kp = 128 if fmt == 4 else 64
+    if qfm.dim() != 4 or tuple(qfm.shape[2:]) != (64, 16) or rows < 1 or qfm.shape[0] != (rows + 15) // 16:
+        raise ValueError(f"{name}: expected [ceil(rows / 16), K / {kp}, 64, 16] bytes for {rows} weight rows, got {tuple(qfm.shape)}")
+    K = qfm.shape[1] * kp
+    if fmt == 4:
+        _chk(sc, torch.uint8, "efm")
+        if tuple(sc.shape) != (qfm.shape[0], qfm.shape[1], 16, 4):
+            raise ValueError(f"{name}: expected efm {(qfm.shape[0], qfm.shape[1], 16, 4)}, got {tuple(sc.shape)}")
+    else:
+        _chk(sc, torch.float32, "scale")
+        if sc.numel() != rows:
+            raise ValueError(f"{name}: expected one scale per weight row ({rows}), got {sc.numel()}")
+    if K == 0 or x.shape[-1] != K:
+        raise ValueError(f"{name}: x[..., {x.shape[-1]}] vs K = {K}")
+    B = x.numel() // K
+    if not 1 <= B <= QFM_MAX_ROWS:
+        raise ValueError(f"{name}: {B} rows of x, the fragment-major weight-only GEMVs exist for 1..{QFM_MAX_ROWS}")
+    return K, B
+
+
+def _qfm_plain(sym, qfm, sc, x, N, bias, res, out, name, fmt):
+    K, B = _chk_qfm(qfm, sc, x, N, name, fmt)
+    for t, n, cnt in ((bias, "bias", N), (res, "res", B * N)):
+        if t is not None:
+            _chk(t, BF16, n)
+            assert t.numel() == cnt, f"{n}: expected {cnt} elements"
+    if out is None:
+        out = torch.empty(B, N, dtype=BF16, device=x.device)
+    _chk(out, BF16, "out")
+    assert out.numel() == B * N
+    _lib.call(sym, _p(qfm), _p(sc), _p(x), _p(out), _p(bias), _p(res), B, N, K, _stream())
+    return out
+
+
+def _qfm_swiglu(sym, qfm, sc, x, out, name, fmt):
+    I = qfm.shape[0] * 16 // 2 if qfm.dim() == 4 else 0
+    if I < 1 or I % 16:
+        raise ValueError(f"{name}: the copy must hold [gate rows | up rows] with I a multiple of 16, got {tuple(qfm.shape)}")
+    K, B = _chk_qfm(qfm, sc, x, 2 * I, name, fmt)
+    if out is None:
+        out = torch.empty(B, I, dtype=BF16, device=x.device)
+    _chk(out, BF16, "out")
+    assert out.numel() == B * I
+    _lib.call(sym, _p(qfm), _p(sc), _p(x), _p(out), B, I, K, _stream())
+    return out
+
+
+def gemv_fm_w4(qfm, efm, x, N, bias=None, res=None, out=None):
+    """`gemv_w4` on the fragment-major copy (qfm, efm) = repack_fm_w4(blocks, scales): out[b, n] = sum_k x[b, k] W_eff[n, k] (+bias)
+    (+res) on the matrix cores, 1 <= B <= 16, K % 128 == 0. No fused RMSNorm: x is used as it is."""
+    return _qfm_plain("spider_gemv_fm_w4", qfm, efm, x, N, bias, res, out, "qfm", 4)
+
+
+def gemv_swiglu_fm_w4(qfm, efm, x, out=None):
+    """`gemv_swiglu_w4` on repack_fm_w4 of [gate rows | up rows] (I % 16 == 0); 1 <= B <= 16."""
+    return _qfm_swiglu("spider_gemv_swiglu_fm_w4", qfm, efm, x, out, "qfm_gate_up", 4)
+
+
+def gemv_fm_w8(qfm, scale, x, N, bias=None, res=None, out=None):
+    """`gemv_w8` on the fragment-major copy qfm = repack_fm_w8(Wq) with the per-row scale [N] fp32 as it is:
+    out[b, n] = scale[n] * sum_k x[b, k] f32(Wq[n, k]) (+bias) (+res) on the matrix cores, 1 <= B <= 16, K % 64 == 0."""
+    return _qfm_plain("spider_gemv_fm_w8", qfm, scale, x, N, bias, res, out, "qfm", 8)
+
+
+def gemv_swiglu_fm_w8(qfm, scale, x, out=None):
+    """`gemv_swiglu_w8` on repack_fm_w8 of [gate rows | up rows] (I % 16 == 0), scale [2 I]; 1 <= B <= 16."""
+    return _qfm_swiglu("spider_gemv_swiglu_fm_w8", qfm, scale, x, out, "qfm_gate_up", 8)
+
+
 def lm_head_argmax_fm(Wfm, x, V, out_ids=None, logits=None, ws=None, norm_eps=None):
     """Greedy argmax of x @ W^T on the fragment-major lm_head copy; 1 <= B <= 16. x normalised, or (norm_eps given, Wfm =
     repack_fm16(W, norm_w)) the un-normalised last hidden state."""

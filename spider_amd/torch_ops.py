@@ -274,6 +274,55 @@ def _(blocks_gate_up, scales, x, norm_w=None, eps=1e-6):
     return x.new_empty(x.numel() // (2 * blocks_gate_up.shape[1]), blocks_gate_up.shape[0] // 2)
 
 
+# ------------------------------------------------------------------------------------------ fragment-major weight-only GEMVs
+@_op("gemv_fm_w4")
+def gemv_fm_w4(qfm: torch.Tensor, efm: torch.Tensor, x: torch.Tensor, n: int, bias: Optional[torch.Tensor] = None,
+               res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemv_w4 for up to 16 rows on (qfm, efm) = ops.repack_fm_w4(blocks, scales): x [B <= 16, K] bf16 -> [B, n] bf16 =
+    x @ W_eff^T (+bias) (+res) on the matrix cores; no fused RMSNorm"""
+    return ops.gemv_fm_w4(qfm, efm, x.contiguous(), n, bias=bias, res=res)
+
+
+@gemv_fm_w4.register_fake
+def _(qfm, efm, x, n, bias=None, res=None):
+    return x.new_empty(x.numel() // (128 * qfm.shape[1]), n)
+
+
+@_op("gemv_swiglu_fm_w4")
+def gemv_swiglu_fm_w4(qfm: torch.Tensor, efm: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """gemv_swiglu_w4 for up to 16 rows on ops.repack_fm_w4 of [gate rows | up rows] (I % 16 == 0); -> [B <= 16, I]"""
+    return ops.gemv_swiglu_fm_w4(qfm, efm, x.contiguous())
+
+
+@gemv_swiglu_fm_w4.register_fake
+def _(qfm, efm, x):
+    return x.new_empty(x.numel() // (128 * qfm.shape[1]), qfm.shape[0] * 8)
+
+
+@_op("gemv_fm_w8")
+def gemv_fm_w8(qfm: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, n: int, bias: Optional[torch.Tensor] = None,
+               res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemv_w8 for up to 16 rows on qfm = ops.repack_fm_w8(wq), scale [n] fp32: x [B <= 16, K] bf16 -> [B, n] bf16 =
+    scale[n] * (x @ f32(wq)^T) (+bias) (+res) on the matrix cores; no fused RMSNorm"""
+    return ops.gemv_fm_w8(qfm, scale, x.contiguous(), n, bias=bias, res=res)
+
+
+@gemv_fm_w8.register_fake
+def _(qfm, scale, x, n, bias=None, res=None):
+    return x.new_empty(x.numel() // (64 * qfm.shape[1]), n)
+
+
+@_op("gemv_swiglu_fm_w8")
+def gemv_swiglu_fm_w8(qfm: torch.Tensor, scale: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """gemv_swiglu_w8 for up to 16 rows on ops.repack_fm_w8 of [gate rows | up rows] (I % 16 == 0), scale [2 I]; -> [B <= 16, I]"""
+    return ops.gemv_swiglu_fm_w8(qfm, scale, x.contiguous())
+
+
+@gemv_swiglu_fm_w8.register_fake
+def _(qfm, scale, x):
+    return x.new_empty(x.numel() // (64 * qfm.shape[1]), qfm.shape[0] * 8)
+
+
 # ------------------------------------------------------------------------------------------ weight-only FP8 / MXFP4 lm_head
 def _as_fp8(q: torch.Tensor) -> torch.Tensor:
     return q.view(ops.FP8) if q.dtype == torch.uint8 else q
@@ -414,13 +463,14 @@ def _(packed_u8, desc, tabs, lut, rows, patch, merge, temporal, tmp_bytes, max_h
     return packed_u8.new_empty(rows, 3 * temporal * patch * patch, dtype=torch.float32 if f32 else BF16)
 
 
-# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 and MXFP4 GEMVs and lm_heads, the safety-checker
+# the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 and MXFP4 GEMVs (row-major and fragment-major) and lm_heads, the safety-checker
 # ops and the audio and image feature ops above are listed apart
 SAFETY_OP_NAMES = ("clip_preprocess", "safety_decide", "image_blackout_")
 AUDIO_OP_NAMES = ("logmel",)
 IMAGE_OP_NAMES = ("qwen_image_patches",)
 W8_OP_NAMES = ("gemv_w8", "gemv_swiglu_w8")
 W4_OP_NAMES = ("gemv_w4", "gemv_swiglu_w4")
+QFM_OP_NAMES = ("gemv_fm_w4", "gemv_swiglu_fm_w4", "gemv_fm_w8", "gemv_swiglu_fm_w8")
 LM_HEAD_Q_OP_NAMES = ("lm_head_argmax_w8", "lm_head_argmax_proc_w8", "lm_head_argmax_w4", "lm_head_argmax_proc_w4")
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
