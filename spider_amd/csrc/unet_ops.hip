@@ -987,7 +987,12 @@ __global__ __launch_bounds__(256) void latent_in_kernel(const float* __restrict_
         const int c = (int)(idx % C);
         const size_t px = (idx / C) % HW;
         const size_t b = idx / ((size_t)C * HW);
-        const h16_t v = f32_to_h16(lat[(b * C + c) * HW + px] * scale);
+        // the product is rounded to fp32 and THEN to the 16-bit format, as written (and as latent_in32_kernel followed by a rounding
+        // does). Left to itself the f16 build selects one v_fma_mixlo_f16 for both steps, which rounds the exact product once: 1 ulp
+        // off the two-step value wherever the fp32 product lands on an f16 tie (7e-5 of the elements). The empty asm keeps the steps apart.
+        float p = lat[(b * C + c) * HW + px] * scale;
+        asm volatile("" : "+v"(p));
+        const h16_t v = f32_to_h16(p);
         for (int r = 0; r < reps; ++r) out[(size_t)r * total + idx] = v;
     }
 }
