@@ -50,19 +50,20 @@ int spider_gemv_bf16(const void* W, const void* x, void* out, const void* bias, 
 int spider_gemv_swiglu_bf16(const void* W_gate_up, const void* x, void* out, const void* norm_w, float eps, int B,
                             int I, int K, void* stream);
 
-/* Weight-only FP8 forms of the two calls above for 1 <= B <= 4 (csrc/gemv_w8.hip): Wq [N, K] bytes in OCP e4m3fn (448 = 0x7e,
+/* Weight-only FP8 forms of the two calls above for 1 <= B <= 4 (csrc/gemv_wq.hip): Wq [N, K] bytes in OCP e4m3fn (448 = 0x7e,
  * 1.0 = 0x38; not MI300's fnuz), scale [N] fp32 per weight row, K % 16 == 0:
  *   out[b,n] = epilogue(scale[n] * sum_k xin[b,k] * f32(Wq[n,k]))
  * with the prologue (fused RMSNorm, normalised activation rounded to bf16) and the epilogue (+bias -> bf16 -> +res -> bf16) of
  * spider_gemv_bf16. The fp32 sum is scaled once, after the reduction. The fused RMSNorm needs the staged
- * activations, B * ceil(K / 1024) * 2 KiB, within the LDS of a CU (160 KiB less 256 bytes). */
+ * activations, B * ceil(K / 1024) * 2 KiB, within the LDS of a CU (160 KiB less 256 bytes).
+ * K % 16, B in 1..4 and null Wq / scale / x / out are refused (-1) before any launch. */
 int spider_gemv_w8(const void* Wq, const float* scale, const void* x, void* out, const void* bias, const void* res,
                    const void* norm_w, float eps, int B, int N, int K, void* stream);
 /* Wq_gate_up [2 I, K] = [gate rows | up rows], scale [2 I]; out[b,i] = bf16(bf16(silu(bf16(g))) * bf16(u)) */
 int spider_gemv_swiglu_w8(const void* Wq_gate_up, const float* scale, const void* x, void* out, const void* norm_w, float eps,
                           int B, int I, int K, void* stream);
 
-/* Weight-only MXFP4 (OCP Microscaling FP4) forms of the same two calls for 1 <= B <= 4 (csrc/gemv_w4.hip), K % 32 == 0:
+/* Weight-only MXFP4 (OCP Microscaling FP4) forms of the same two calls for 1 <= B <= 4 (csrc/gemv_wq.hip), K % 32 == 0:
  *   blocks [N, K / 2] bytes, row-major: byte j of row n holds weight 2 j in its low nibble and weight 2 j + 1 in its high nibble; a
  *          nibble code c has sign bit 3 and magnitude {0, .5, 1, 1.5, 2, 3, 4, 6}[c & 7] (e2m1)
  *   scales [N, K / 32] bytes, row-major, E8M0: weights 32 g .. 32 g + 31 of row n are multiplied by 2^(scales[n, g] - 127); bytes 1..254

@@ -7,7 +7,7 @@ DESIGN.md section 5 a difference below 3 % is no difference: FP8_MAX_ROWS is the
 
 Second part (alone with --ops-only): the four projections by themselves, captured launches cycling through the 28 layers'
 weights (233 MB of e4m3 or 466 MB of bf16 per layer, so no launch finds its weights in the 256 MB Infinity Cache), FP8 against
-the bf16 kernel of the same route -- which projection pays. The dispatch of csrc/gemv_w8.hip can be varied from the environment
+the bf16 kernel of the same route -- which projection pays. The dispatch of csrc/gemv_wq.hip can be varied from the environment
 (SPIDER_W8_NWB, SPIDER_W8_R, SPIDER_W8_GU_R, SPIDER_W8_LDS_MAX), one process per setting.
 
     python scripts/exp/fp8_decode_cost.py [--out FILE] [--rows 1,2,3,4] [--ops-only]"""

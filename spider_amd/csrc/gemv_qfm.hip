@@ -19,7 +19,7 @@
 // natural k order with rows >= B read as zeros through the buffer range, partial tiles summed through LDS by wave 0.
 // What differs is the weight decode in front of v_mfma_f32_16x16x32_bf16:
 //   MXFP4: four v_cvt_scalef32_pk_bf16_fp4 per sub-step (one per weight byte) with the f32 scale operand uint32(byte) << 23, as in
-//          gemv_w4.hip: exact (two significand bits times a power of two).
+//          gemv_wq.hip: exact (two significand bits times a power of two).
 //   FP8:   four v_cvt_scalef32_pk_bf16_fp8 per sub-step with the scale operand 1.0f, and scale[n] applied to the fp32 accumulators
 //          in the epilogue, instead of the row's scale as the conversion's operand. Read from the ISA: either form is one conversion
 //          per two weights, so they cost the same VALU work; this one needs no per-lane scale register in the loop, multiplies the
@@ -27,22 +27,11 @@
 // Loads past a wave's K range use the all-ones offset of skinny_fm_kernel: weights, activations AND the MXFP4 scale dword read as
 // zeros. Scale byte 0 is the operand +0.0f, whose exponent field the conversion reads as 2^-127; the nibbles beside it are code 0, and
 // 0 * 2^-127 = 0 meets a zero activation: the sub-step adds +0 to the accumulator. No NaN can arise (only byte 255 is one).
-#include "common.hpp"
-#include <stdio.h>
-#include <stdlib.h>
+#include "wq_common.hpp"
 
 using namespace spider;
 
 namespace {
-
-template <int SEL>
-__device__ __forceinline__ uint32_t qfm_fp4x2(uint32_t w, float sc) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, SEL));
-}
-template <bool HI>
-__device__ __forceinline__ uint32_t qfm_fp8x2(uint32_t w) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-}
 
 // FMT: 4 = MXFP4 (SUB = 4 sub-steps of 32 weights per piece), 8 = FP8 (SUB = 2). MODE 0 / 1 as above. D: pieces in flight per wave.
 template <int FMT, int MODE, int NW, int D>
@@ -104,11 +93,11 @@ __global__ __launch_bounds__(NW * 64) void qfm_kernel(const uint8_t* __restrict_
                     u32x4 a;
                     if (FMT == 4) {
                         const uint32_t w = wq[s][t][sx];
-                        const float sc = __builtin_bit_cast(float, ((eq[s][t] >> (8 * sx)) & 0xffu) << 23);
-                        a[0] = qfm_fp4x2<0>(w, sc); a[1] = qfm_fp4x2<1>(w, sc); a[2] = qfm_fp4x2<2>(w, sc); a[3] = qfm_fp4x2<3>(w, sc);
+                        const float sc = e8m0_to_f32((eq[s][t] >> (8 * sx)) & 0xffu);
+                        a[0] = fp4x2_to_bf16x2<0>(w, sc); a[1] = fp4x2_to_bf16x2<1>(w, sc); a[2] = fp4x2_to_bf16x2<2>(w, sc); a[3] = fp4x2_to_bf16x2<3>(w, sc);
                     } else {
                         const uint32_t w0 = wq[s][t][2 * sx], w1 = wq[s][t][2 * sx + 1];
-                        a[0] = qfm_fp8x2<false>(w0); a[1] = qfm_fp8x2<true>(w0); a[2] = qfm_fp8x2<false>(w1); a[3] = qfm_fp8x2<true>(w1);
+                        a[0] = fp8x2_to_bf16x2<false>(w0); a[1] = fp8x2_to_bf16x2<true>(w0); a[2] = fp8x2_to_bf16x2<false>(w1); a[3] = fp8x2_to_bf16x2<true>(w1);
                     }
                     acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), xf, acc[t], 0, 0, 0);
                 }
@@ -153,7 +142,6 @@ __global__ __launch_bounds__(NW * 64) void qfm_kernel(const uint8_t* __restrict_
 
 // everything a launch relies on, checked on the host before any launch. rows = weight rows of the copy (N, or 2 I).
 int qfm_check(const char* who, int fmt, const void* qfm, const void* sc, const void* x, const void* out, int B, int N, int K, bool gateup) {
-    static thread_local char msg[192];
     const int kp = fmt == 4 ? 128 : 64;
     const char* why = nullptr;
     if (N <= 0 || K <= 0 || K % kp != 0) why = fmt == 4 ? "K must be a positive multiple of 128 (one piece is 16 rows x 128 weights)"
@@ -165,10 +153,7 @@ int qfm_check(const char* who, int fmt, const void* qfm, const void* sc, const v
         const size_t groups = (size_t)(gateup ? 2 : 1) * ((N + 15) / 16);
         if (groups * 16 * K / (fmt == 4 ? 2 : 1) >= ((size_t)1 << 32) || (size_t)B * K * 2 >= ((size_t)1 << 32)) why = "weight copy must be < 4 GiB";
     }
-    if (!why) return 0;
-    snprintf(msg, sizeof(msg), "%s: %s", who, why);
-    spider_set_error(msg);
-    return -1;
+    return why ? wq_fail(who, why) : 0;
 }
 
 // Pieces in flight per wave: 2, as skinny_fm_kernel keeps two k blocks. Measured against 4 (scripts/exp/qfm_decode_cost.py --ops-only
@@ -181,7 +166,7 @@ template <int FMT, int MODE>
 int qfm_launch(const void* qfm, const void* efm, const float* scale, const void* x, void* out, const void* bias, const void* res,
                int B, int N, int K, void* stream) {
     // tuning aid, read once: SPIDER_QFM_D = 2 / 4 pieces in flight for both formats
-    static const int env_d = [] { const char* e = getenv("SPIDER_QFM_D"); return e ? atoi(e) : 0; }();
+    static const int env_d = wq_env("SPIDER_QFM_D", 0);
     const int d = (env_d == 2 || env_d == 4) ? env_d : 2;
     const int NG = (N + 15) / 16;
     const size_t groups = (size_t)(MODE == 1 ? 2 : 1) * NG;

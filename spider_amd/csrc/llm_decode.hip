@@ -13,6 +13,7 @@
 // transposed); KV cache [B, n_kv, T_max, d] bf16. All reductions accumulate in fp32.
 #include "common.hpp"
 #include "select.hpp"
+#include "wq_common.hpp"
 #include <stdlib.h>
 
 using namespace spider;
@@ -168,10 +169,10 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16_t* __restrict__
 //   0  one request at a time: U chunks per row requested before the prologue (`hoist`), the prologue loads one x
 //      vector per thread and waits for it (twice over in the normalised form, which reads x again and norm_w only
 //      after the sum of squares), and the k loop requests a chunk set only after the previous one is consumed.
-//   2  one trip for the prologue: a thread requests its first GEMV_STAGE_CAP (4 or 6) vectors of x (x and norm_w in the
+//   2  one trip for the prologue: a thread requests its first stage_cap (4 or 6) vectors of x (x and norm_w in the
 //      normalised form) FIRST, then the hoisted weight chunks, so that the wait for x leaves the weight loads in
 //      flight (vmcnt retires in order); x stays in registers from the sum of squares to the normalise pass. Longer
-//      rows go on in batches of GEMV_STAGE_CAP. Loads are unconditional on clamped addresses (a load under a
+//      rows go on in batches of stage_cap. Loads are unconditional on clamped addresses (a load under a
 //      per-lane branch makes the compiler drain the queue); only the FMAs are predicated by k < K.
 //      With 8 waves per block (NWB = 8: the long-K form, the down projection) the k loop holds two register sets:
 //      set i+1 is requested before set i is consumed, so the wait in front of the FMAs is a counted one.
@@ -181,10 +182,8 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16_t* __restrict__
 // SCHED 1 / 2 also take the RMSNorm block sum and the per-row dot reduction through wave_sum_valu (common.hpp: DPP and
 // v_permlane*_swap in wave_sum's xor order, so the same bits) where SCHED 0 keeps wave_sum's six ds_bpermute round trips.
 // ----------------------------------------------------------------------------------------------
-// 16-byte vectors a thread keeps in flight while it stages the activations (SCHED 1 / 2): one batch covers K <= 8192 (plain) or
-// 4096 (normalised: half of them are norm_w) with 4 waves per block, K <= 24576 with 8 (the down projection asks for 5)
-constexpr int GEMV_STAGE_CAP(int nwb) { return nwb == 8 ? 6 : 4; }
-
+// The staging itself is stage_rows_simple (SCHED 0) / stage_rows_branchfree (SCHED 1 / 2) of wq_common.hpp, shared with the
+// quantised streams.
 template <int NB, int R, bool GATEUP, bool XLDS, int NWB = 4, int SCHED = 0>
 __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict__ W, const bf16_t* __restrict__ x,
                                                    bf16_t* __restrict__ out, const bf16_t* __restrict__ bias,
@@ -223,97 +222,8 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
                 }
             }
         }
-
-        if (XLDS) {
-            const int nv = K / 8;
-            for (int b = 0; b < NB; ++b) {
-                const u32x4* xv = reinterpret_cast<const u32x4*>(x + (size_t)b * K);
-                u32x4* sv = reinterpret_cast<u32x4*>(xs + (size_t)b * K);
-                if (norm_w) {
-                    float ss = 0.f;
-                    for (int i = threadIdx.x; i < nv; i += NWB * 64) {
-                        u32x4 a = xv[i];
-                        uint32_t aw[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            float lo = bf16lo_to_f32(aw[j]), hi = bf16hi_to_f32(aw[j]);
-                            ss += lo * lo + hi * hi;
-                        }
-                    }
-                    const float rs = rsqrtf(block_sum<NWB>(ss, red) / (float)K + eps);
-                    const u32x4* wv = reinterpret_cast<const u32x4*>(norm_w);
-                    for (int i = threadIdx.x; i < nv; i += NWB * 64) {
-                        u32x4 a = xv[i], wq = wv[i];
-                        uint32_t aw[4] = {a.x, a.y, a.z, a.w}, ww[4] = {wq.x, wq.y, wq.z, wq.w}, o[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            float lo = bf16_to_f32(f32_to_bf16(bf16lo_to_f32(aw[j]) * rs)) * bf16lo_to_f32(ww[j]);
-                            float hi = bf16_to_f32(f32_to_bf16(bf16hi_to_f32(aw[j]) * rs)) * bf16hi_to_f32(ww[j]);
-                            o[j] = pack_bf16x2(lo, hi);
-                        }
-                        u32x4 ov;
-                        ov.x = o[0]; ov.y = o[1]; ov.z = o[2]; ov.w = o[3];
-                        sv[i] = ov;
-                    }
-                } else {
-                    for (int i = threadIdx.x; i < nv; i += NWB * 64) sv[i] = xv[i];
-                }
-            }
-            __syncthreads();
-        }
-
+        if (XLDS) stage_rows_simple<NB, NWB>(x, norm_w, eps, K, K / 8, reinterpret_cast<u32x4*>(xs), red, [](int i) { return i; });
     } else {
-        // Branch-free staging: every load goes to a clamped index, a vector past the end of the row counts as zero in the sum of
-        // squares (adding +0 is exact) and is stored, normalised or not, to the clamped slot, where every writer has the same value.
-        constexpr int NT = NWB * 64, CAP = GEMV_STAGE_CAP(NWB), CH = CAP / 2;
-        const int nv = K / 8, t0 = threadIdx.x;
-        const u32x4* wv = reinterpret_cast<const u32x4*>(norm_w);
-        u32x4 st[CAP];
-        auto issue_x = [&](const u32x4* xv, int i0) {     // plain form: CAP vectors of x
-#pragma unroll
-            for (int c = 0; c < CAP; ++c) st[c] = xv[min(i0 + c * NT, nv - 1)];
-        };
-        auto issue_xw = [&](const u32x4* xv, int i0) {    // normalised form: CH vectors of x, then the same CH of norm_w
-#pragma unroll
-            for (int c = 0; c < CH; ++c) st[c] = xv[min(i0 + c * NT, nv - 1)];
-#pragma unroll
-            for (int c = 0; c < CH; ++c) st[CH + c] = wv[min(i0 + c * NT, nv - 1)];
-        };
-        auto store_x = [&](u32x4* sv, int i0) {
-#pragma unroll
-            for (int c = 0; c < CAP; ++c) sv[min(i0 + c * NT, nv - 1)] = st[c];
-        };
-        auto sumsq = [&](float ss, int i0, int n) {
-#pragma unroll
-            for (int c = 0; c < CAP; ++c) {
-                if (c < n) {
-                    const bool in = i0 + c * NT < nv;
-                    uint32_t aw[4] = {in ? st[c].x : 0u, in ? st[c].y : 0u, in ? st[c].z : 0u, in ? st[c].w : 0u};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float lo = bf16lo_to_f32(aw[j]), hi = bf16hi_to_f32(aw[j]);
-                        ss += lo * lo + hi * hi;
-                    }
-                }
-            }
-            return ss;
-        };
-        auto norm_store = [&](u32x4* sv, int i0, float rs) {
-#pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                const u32x4 a = st[c], wq = st[CH + c];
-                uint32_t aw[4] = {a.x, a.y, a.z, a.w}, ww[4] = {wq.x, wq.y, wq.z, wq.w}, o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float lo = bf16_to_f32(f32_to_bf16(bf16lo_to_f32(aw[j]) * rs)) * bf16lo_to_f32(ww[j]);
-                    float hi = bf16_to_f32(f32_to_bf16(bf16hi_to_f32(aw[j]) * rs)) * bf16hi_to_f32(ww[j]);
-                    o[j] = pack_bf16x2(lo, hi);
-                }
-                u32x4 ov;
-                ov.x = o[0]; ov.y = o[1]; ov.z = o[2]; ov.w = o[3];
-                sv[min(i0 + c * NT, nv - 1)] = ov;
-            }
-        };
         auto hoist_w = [&]() {
 #pragma unroll
             for (int u = 0; u < H; ++u) {
@@ -323,48 +233,9 @@ __global__ __launch_bounds__(NWB * 64) void gemv_kernel(const bf16_t* __restrict
                     w0[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + (unsigned)(k < K ? k : K - 8)));
             }
         };
-        // Three straight-line forms, each with the first batch of row 0 requested BEFORE the weights: vmcnt retires in order, so the
-        // wait for that batch leaves the weight loads in flight (any later batch or row waits for them too).
-        const u32x4* xv = reinterpret_cast<const u32x4*>(x);
-        u32x4* sv = reinterpret_cast<u32x4*>(xs);
-        if (!XLDS) {
-            hoist_w();
-        } else if (!norm_w) {
-            issue_x(xv, t0);
-            hoist_w();
-            store_x(sv, t0);
-            // keeps these stores out of the loop below: merged with its stores they would sit behind the loop's wait for ALL loads
-            asm volatile("" ::: "memory");
-            for (int b = 0; b < NB; ++b)
-                for (int i0 = b ? 0 : CAP * NT; i0 < nv; i0 += CAP * NT) {
-                    issue_x(xv + (size_t)b * nv, i0 + t0);
-                    store_x(sv + (size_t)b * nv, i0 + t0);
-                }
-        } else if (nv <= CH * NT) {
-            // the row fits the registers: x is read once and norm_w is requested with it
-            issue_xw(xv, t0);
-            hoist_w();
-            for (int b = 0; b < NB; ++b) {
-                if (b) issue_xw(xv + (size_t)b * nv, t0);
-                const float rs = rsqrtf(block_sum<NWB, true>(sumsq(0.f, t0, CH), red) / (float)K + eps);
-                norm_store(sv + (size_t)b * nv, t0, rs);
-            }
-        } else {
-            hoist_w();
-            for (int b = 0; b < NB; ++b) {
-                float ss = 0.f;
-                for (int i0 = 0; i0 < nv; i0 += CAP * NT) {
-                    issue_x(xv + (size_t)b * nv, i0 + t0);
-                    ss = sumsq(ss, i0 + t0, CAP);
-                }
-                const float rs = rsqrtf(block_sum<NWB, true>(ss, red) / (float)K + eps);
-                for (int i0 = 0; i0 < nv; i0 += CH * NT) {
-                    issue_xw(xv + (size_t)b * nv, i0 + t0);
-                    norm_store(sv + (size_t)b * nv, i0 + t0, rs);
-                }
-            }
-        }
-        if (XLDS) __syncthreads();
+        // the branch-free staging of wq_common.hpp, rows in natural order: the first batch of x is requested before the weights
+        if (!XLDS) hoist_w();
+        else stage_rows_branchfree<NB, NWB>(x, norm_w, eps, K, K / 8, reinterpret_cast<u32x4*>(xs), red, [](int i) { return i; }, hoist_w);
     }
 
     if (col0 >= N) return;
@@ -546,41 +417,7 @@ __global__ __launch_bounds__(256) void lmhead_partial_kernel(const bf16_t* __res
     __shared__ float bval[4][NB];
     __shared__ int bidx[4][NB];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nv = K / 8;
-    for (int b = 0; b < NB; ++b) {
-        const u32x4* xv = reinterpret_cast<const u32x4*>(x + (size_t)b * K);
-        u32x4* sv = reinterpret_cast<u32x4*>(xs + (size_t)b * K);
-        if (norm_w) {
-            float ss = 0.f;
-            for (int i = threadIdx.x; i < nv; i += 256) {
-                u32x4 a = xv[i];
-                uint32_t aw[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float lo = bf16lo_to_f32(aw[j]), hi = bf16hi_to_f32(aw[j]);
-                    ss += lo * lo + hi * hi;
-                }
-            }
-            const float rs = rsqrtf(block_sum<4>(ss, red) / (float)K + eps);
-            const u32x4* wv = reinterpret_cast<const u32x4*>(norm_w);
-            for (int i = threadIdx.x; i < nv; i += 256) {
-                u32x4 a = xv[i], wq = wv[i];
-                uint32_t aw[4] = {a.x, a.y, a.z, a.w}, ww[4] = {wq.x, wq.y, wq.z, wq.w}, o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float lo = bf16_to_f32(f32_to_bf16(bf16lo_to_f32(aw[j]) * rs)) * bf16lo_to_f32(ww[j]);
-                    float hi = bf16_to_f32(f32_to_bf16(bf16hi_to_f32(aw[j]) * rs)) * bf16hi_to_f32(ww[j]);
-                    o[j] = pack_bf16x2(lo, hi);
-                }
-                u32x4 ov;
-                ov.x = o[0]; ov.y = o[1]; ov.z = o[2]; ov.w = o[3];
-                sv[i] = ov;
-            }
-        } else {
-            for (int i = threadIdx.x; i < nv; i += 256) sv[i] = xv[i];
-        }
-    }
-    __syncthreads();
+    stage_rows_simple<NB, 4>(x, norm_w, eps, K, K / 8, reinterpret_cast<u32x4*>(xs), red, [](int i) { return i; });
 
     float best[NB];
     int besti[NB];
@@ -653,35 +490,6 @@ __global__ __launch_bounds__(256) void lmhead_partial_kernel(const bf16_t* __res
         pval[(size_t)b * gridDim.x + blockIdx.x] = bv;
         pidx[(size_t)b * gridDim.x + blockIdx.x] = bi;
     }
-}
-
-__global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ pval, const int* __restrict__ pidx,
-                                                           int* __restrict__ out, int nparts) {
-    __shared__ float sv[256];
-    __shared__ int si[256];
-    const int b = blockIdx.x;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < nparts; i += 256) {
-        const float v = pval[(size_t)b * nparts + i];
-        const int ix = pidx[(size_t)b * nparts + i];
-        if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
-    }
-    sv[threadIdx.x] = bv;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            const float v = sv[threadIdx.x + s];
-            const int ix = si[threadIdx.x + s];
-            if (v > sv[threadIdx.x] || (v == sv[threadIdx.x] && ix < si[threadIdx.x])) {
-                sv[threadIdx.x] = v;
-                si[threadIdx.x] = ix;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[b] = si[0];
 }
 
 // End of a decode step, one launch instead of five elementwise ones: the token just chosen becomes the next input, the

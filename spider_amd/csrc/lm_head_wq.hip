@@ -3,16 +3,16 @@
 //
 //   logit[b, n] = bf16( sum_k xin[b, k] * W_eff[n, k] ),   b < NB <= 4,   n < V
 //   FP8   (spider_lm_head_argmax[_proc]_w8): q [V, K] bytes, OCP e4m3fn, K % 16 == 0; scale [V] fp32, one per vocabulary row;
-//         W_eff[n, k] = f32(q[n, k]) * scale[n]  (the layout of spider_amd/llm.py: quantize_fp8_rows, as gemv_w8.hip reads it)
+//         W_eff[n, k] = f32(q[n, k]) * scale[n]  (the layout of spider_amd/llm.py: quantize_fp8_rows, as gemv_wq.hip reads it)
 //   MXFP4 (spider_lm_head_argmax[_proc]_w4): blocks [V, K / 2] bytes, two e2m1 codes per byte, low nibble first, K % 32 == 0;
 //         scales [V, K / 32] bytes, E8M0, 1..254; W_eff[n, k] = e2m1(code) * 2^(scales[n, k / 32] - 127)  (quantize_mxfp4, as
-//         gemv_w4.hip reads it)
+//         gemv_wq.hip reads it)
 //   xin   x, or the final RMSNorm in the two-rounding form of lmhead_partial_kernel: bf16(bf16(x * rs) * norm_w), with the sum of
 //         squares reduced in that kernel's order
 //
 // Contract of lmhead_partial_kernel, kept: grid = spider_lm_head_nparts(V) blocks of 4 waves, each block owns a contiguous range of
 // vocabulary rows and writes one (value, index) partial per sequence into the [B, nparts] workspace, which the final reduction
-// (argmax_final below, the bf16 form's kernel restated) turns into out_ids. The epilogue is the bf16 kernel's: the logit is rounded
+// (argmax_final_kernel of wq_common.hpp, the bf16 form's) turns into out_ids. The epilogue is the bf16 kernel's: the logit is rounded
 // to bf16, optionally stored RAW to logits [B, V], widened to fp32, passed through lm_proc_flags / lm_proc_apply in the PROC form,
 // and kept when lv > best || (lv == best && n < besti): ties and an all -inf row go to the lowest id.
 //
@@ -20,7 +20,7 @@
 // and the row's fp32 scale multiplies the fp32 sum once after the wave reduction. MXFP4: a lane's 16-byte load is 32 weights = one
 // MX block with one scale byte, v_cvt_scalef32_pk_bf16_fp4 with the scale uint32(byte) << 23 applied inside the conversion. Both
 // meet the activations in v_dot2c_f32_bf16. Activations are staged once per block in LDS, rows padded to whole chunks (1024 / 2048
-// elements) and swizzled per chunk (w8_slot / w4_slot of the siblings) so that every 16-byte LDS read is lane-contiguous; the
+// elements) and swizzled per chunk (wq_slot of wq_common.hpp) so that every 16-byte LDS read is lane-contiguous; the
 // siblings' budget rule decides whether they fit (ops.w8_norm_fits / w4_norm_fits), else x is read through L2 and the fused norm is
 // refused. Loads go to clamped addresses (row min(n, V - 1), k min(k, K - 16 / 32)); only the FMAs and the epilogue are predicated.
 // Unlike the siblings the weights are decoded one 8-weight piece at a time next to the activations' LDS read, so at most four
@@ -37,10 +37,8 @@
 // or three waves per SIMD); the default LMQ_R_DEFAULT = 4 is what every other figure of that file was taken with. From three
 // sequences on the launch is no longer bound by the weight stream (MXFP4: 3.4 / 2.6 TB/s at 3 / 4 sequences against 4.9 at one).
 // Issuing the next group's loads before the current group's reduction was not built or measured.
-#include "common.hpp"
 #include "select.hpp"
-#include <stdio.h>
-#include <stdlib.h>
+#include "wq_common.hpp"
 
 using namespace spider;
 
@@ -48,27 +46,7 @@ extern "C" int spider_lm_head_nparts(int V);     // llm_decode.hip: blocks = par
 
 namespace {
 
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
 #define LMQ_R_DEFAULT 4                          // vocabulary rows per wave iteration
-#define LMQ_LDS_BUDGET_BYTES (160 * 1024 - 256)  // staged activations per block: the siblings' W8 / W4_LDS_BUDGET_BYTES
-
-// 16-byte vector i of an activation row (elements 8 i .. 8 i + 7) -> its vector slot in the swizzled LDS row (gemv_w8 / gemv_w4)
-__device__ __forceinline__ int w8_slot(int i) { return (i & ~127) | ((i & 1) << 6) | ((i & 127) >> 1); }
-__device__ __forceinline__ int w4_slot(int i) { return (i & ~255) | ((i & 3) << 6) | ((i & 255) >> 2); }
-
-// 4 e4m3 bytes -> two packed bf16 pairs (bytes 0,1 | bytes 2,3), exact
-__device__ __forceinline__ void fp8x4_to_bf16x4(uint32_t w, uint32_t& lo, uint32_t& hi) {
-    const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
-    const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
-    lo = pack_bf16x2(a[0], a[1]);
-    hi = pack_bf16x2(b[0], b[1]);
-}
-// byte `SEL` of w (two e2m1 codes, low nibble first) times the block scale -> a packed bf16 pair, exact
-template <int SEL>
-__device__ __forceinline__ uint32_t fp4x2_to_bf16x2(uint32_t w, float sc) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, SEL));
-}
 
 // FMT 8: FP8 bytes + fp32 row scales; FMT 4: MXFP4 nibbles + E8M0 block scale bytes
 template <int FMT, int NB, int R, bool PROC, bool XLDS>
@@ -82,8 +60,7 @@ __global__ __launch_bounds__(256) void lmq_partial_kernel(const uint8_t* __restr
     __shared__ float red[4];
     __shared__ float bval[4][NB];
     __shared__ int bidx[4][NB];
-    constexpr int LW = FMT == 8 ? 16 : 32;       // weights per lane per 16-byte load
-    constexpr int CHUNK = 64 * LW;               // weights per wave instruction
+    constexpr int LW = WQ_LW<FMT>, CHUNK = WQ_CHUNK<FMT>;
     constexpr int NP = LW / 8;                   // 8-weight pieces (one weight word of FP4, two of FP8) = 16-byte LDS reads per load
     constexpr int U = 2;                         // chunks of every row requested before the first FMA
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -94,43 +71,8 @@ __global__ __launch_bounds__(256) void lmq_partial_kernel(const uint8_t* __restr
 
     // ---- activations: lmhead_partial_kernel's staging (same sum-of-squares order, same two roundings), to swizzled padded rows.
     // The pad past K is never written and never read: a lane's LW weights are wholly inside the row or wholly past it.
-    if constexpr (XLDS) {
-        const int nv = K / 8, nvp = KP / 8;
-        for (int b = 0; b < NB; ++b) {
-            const u32x4* xv = reinterpret_cast<const u32x4*>(x + (size_t)b * K);
-            u32x4* sv = reinterpret_cast<u32x4*>(smem) + (size_t)b * nvp;
-            if (norm_w) {
-                float ss = 0.f;
-                for (int i = threadIdx.x; i < nv; i += 256) {
-                    u32x4 a = xv[i];
-                    uint32_t aw[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float lo = bf16lo_to_f32(aw[j]), hi = bf16hi_to_f32(aw[j]);
-                        ss += lo * lo + hi * hi;
-                    }
-                }
-                const float rs = rsqrtf(block_sum<4>(ss, red) / (float)K + eps);
-                const u32x4* wv = reinterpret_cast<const u32x4*>(norm_w);
-                for (int i = threadIdx.x; i < nv; i += 256) {
-                    u32x4 a = xv[i], wq = wv[i];
-                    uint32_t aw[4] = {a.x, a.y, a.z, a.w}, ww[4] = {wq.x, wq.y, wq.z, wq.w}, o[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float lo = bf16_to_f32(f32_to_bf16(bf16lo_to_f32(aw[j]) * rs)) * bf16lo_to_f32(ww[j]);
-                        float hi = bf16_to_f32(f32_to_bf16(bf16hi_to_f32(aw[j]) * rs)) * bf16hi_to_f32(ww[j]);
-                        o[j] = pack_bf16x2(lo, hi);
-                    }
-                    u32x4 ov;
-                    ov.x = o[0]; ov.y = o[1]; ov.z = o[2]; ov.w = o[3];
-                    sv[FMT == 8 ? w8_slot(i) : w4_slot(i)] = ov;
-                }
-            } else {
-                for (int i = threadIdx.x; i < nv; i += 256) sv[FMT == 8 ? w8_slot(i) : w4_slot(i)] = xv[i];
-            }
-        }
-        __syncthreads();
-    }
+    if constexpr (XLDS)
+        stage_rows_simple<NB, 4>(x, norm_w, eps, K, KP / 8, reinterpret_cast<u32x4*>(smem), red, [](int i) { return wq_slot<FMT>(i); });
     const bf16_t* xs = reinterpret_cast<const bf16_t*>(smem);
 
     float best[NB];
@@ -190,16 +132,7 @@ __global__ __launch_bounds__(256) void lmq_partial_kernel(const uint8_t* __restr
                         for (int r = 0; r < R; ++r) {
                             const uint32_t ww[4] = {wq[u][r].x, wq[u][r].y, wq[u][r].z, wq[u][r].w};
                             uint32_t wb[4];
-                            if constexpr (FMT == 8) {
-                                fp8x4_to_bf16x4(ww[2 * p], wb[0], wb[1]);
-                                fp8x4_to_bf16x4(ww[2 * p + 1], wb[2], wb[3]);
-                            } else {
-                                const float s = __builtin_bit_cast(float, sb[u][r] << 23);
-                                wb[0] = fp4x2_to_bf16x2<0>(ww[p], s);
-                                wb[1] = fp4x2_to_bf16x2<1>(ww[p], s);
-                                wb[2] = fp4x2_to_bf16x2<2>(ww[p], s);
-                                wb[3] = fp4x2_to_bf16x2<3>(ww[p], s);
-                            }
+                            wq_decode_piece<FMT>(ww, p, sb[u][r], wb);
 #pragma unroll
                             for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -249,44 +182,6 @@ __global__ __launch_bounds__(256) void lmq_partial_kernel(const uint8_t* __restr
     }
 }
 
-// argmax_final_kernel of llm_decode.hip restated, so that this translation unit launches only kernels it defines: one block per
-// sequence reduces the [nparts] partials, ties -> lowest id
-__global__ __launch_bounds__(256) void lmq_argmax_final_kernel(const float* __restrict__ pval, const int* __restrict__ pidx,
-                                                               int* __restrict__ out, int nparts) {
-    __shared__ float sv[256];
-    __shared__ int si[256];
-    const int b = blockIdx.x;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < nparts; i += 256) {
-        const float v = pval[(size_t)b * nparts + i];
-        const int ix = pidx[(size_t)b * nparts + i];
-        if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
-    }
-    sv[threadIdx.x] = bv;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            const float v = sv[threadIdx.x + s];
-            const int ix = si[threadIdx.x + s];
-            if (v > sv[threadIdx.x] || (v == sv[threadIdx.x] && ix < si[threadIdx.x])) {
-                sv[threadIdx.x] = v;
-                si[threadIdx.x] = ix;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[b] = si[0];
-}
-
-constexpr size_t LMQ_LDS_DEFAULT_LIMIT = 64 * 1024 - 256, LMQ_LDS_HW_LIMIT = 160 * 1024 - 256;
-
-int lmq_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 struct LmqArgs {
     const void *q, *scale, *x, *norm_w;
     float eps;
@@ -299,9 +194,9 @@ struct LmqArgs {
 template <int FMT, int NB, int R, bool PROC, bool XL>
 void lmq_launch(const LmqArgs& a, const LmProc& pr, int nparts, size_t lds) {
     auto* fn = lmq_partial_kernel<FMT, NB, R, PROC, XL>;
-    if (XL && lds > LMQ_LDS_DEFAULT_LIMIT) {
+    if (XL && lds > WQ_LDS_DEFAULT_LIMIT) {
         static unsigned raised = 0;
-        raise_dynamic_lds(fn, (int)LMQ_LDS_HW_LIMIT, raised);
+        raise_dynamic_lds(fn, (int)WQ_LDS_HW_LIMIT, raised);
     }
     fn<<<nparts, 256, XL ? lds : 0, (hipStream_t)a.stream>>>((const uint8_t*)a.q, a.scale, (const bf16_t*)a.x, (const bf16_t*)a.norm_w,
                                                               a.eps, (float*)a.ws_val, (int*)a.ws_idx, (bf16_t*)a.logits, a.V, a.K, pr);
@@ -311,16 +206,10 @@ template <int FMT, int NB, bool PROC>
 int lmq_dispatch(const LmqArgs& a, const LmProc& pr) {
     // tuning aids, read once: SPIDER_W8_LDS_MAX / SPIDER_W4_LDS_MAX (the siblings' budget of staged activations per block, which
     // ops.w8_norm_fits / w4_norm_fits mirror), SPIDER_LMQ_R (vocabulary rows per wave iteration: 2 / 4 / 8)
-    static const size_t lds_max = [] {
-        const int v = lmq_env(FMT == 8 ? "SPIDER_W8_LDS_MAX" : "SPIDER_W4_LDS_MAX", 0);
-        return v > 0 ? ((size_t)v < LMQ_LDS_HW_LIMIT ? (size_t)v : LMQ_LDS_HW_LIMIT) : (size_t)LMQ_LDS_BUDGET_BYTES;
-    }();
-    static const int env_r = lmq_env("SPIDER_LMQ_R", 0);
-    constexpr int CHUNK = FMT == 8 ? 1024 : 2048;
-    const size_t lds = (size_t)NB * ((a.K + CHUNK - 1) / CHUNK) * CHUNK * 2;     // rows padded to whole chunks
-    const bool xlds = lds <= lds_max;
-    if (FMT == 8) SPIDER_CHECK(xlds || a.norm_w == nullptr, "lm_head_argmax_w8: fused RMSNorm needs the activations in LDS (batch * ceil(K / 1024) * 2 KiB within the budget)");
-    else SPIDER_CHECK(xlds || a.norm_w == nullptr, "lm_head_argmax_w4: fused RMSNorm needs the activations in LDS (batch * ceil(K / 2048) * 4 KiB within the budget)");
+    static const int env_r = wq_env("SPIDER_LMQ_R", 0);
+    const size_t lds = wq_lds_bytes<FMT>(NB, a.K);
+    const bool xlds = lds <= wq_lds_max<FMT>();
+    if (!xlds && a.norm_w) return wq_fail(FMT == 8 ? "lm_head_argmax_w8" : "lm_head_argmax_w4", WQ_NORM_RULE<FMT>);
     const int nparts = spider_lm_head_nparts(a.V);
     const int R = (env_r == 2 || env_r == 4 || env_r == 8) ? env_r : LMQ_R_DEFAULT;
     if (!xlds) lmq_launch<FMT, NB, LMQ_R_DEFAULT, PROC, false>(a, pr, nparts, 0);     // activations through L2: one form
@@ -328,7 +217,7 @@ int lmq_dispatch(const LmqArgs& a, const LmProc& pr) {
     else if (R == 4) lmq_launch<FMT, NB, 4, PROC, true>(a, pr, nparts, lds);
     else lmq_launch<FMT, NB, 8, PROC, true>(a, pr, nparts, lds);
     SPIDER_LAUNCH_OK();
-    lmq_argmax_final_kernel<<<a.B, 256, 0, (hipStream_t)a.stream>>>((const float*)a.ws_val, (const int*)a.ws_idx, a.out_ids, nparts);
+    argmax_final_kernel<<<a.B, 256, 0, (hipStream_t)a.stream>>>((const float*)a.ws_val, (const int*)a.ws_idx, a.out_ids, nparts);
     SPIDER_LAUNCH_OK();
     return 0;
 }
@@ -336,18 +225,11 @@ int lmq_dispatch(const LmqArgs& a, const LmProc& pr) {
 // everything a launch relies on, checked on the host before any launch
 template <int FMT>
 int lmq_check(const char* who, const LmqArgs& a) {
-    static thread_local char msg[200];
-    const char* why = nullptr;
-    if (a.V <= 0 || a.K <= 0 || a.K % (FMT == 8 ? 16 : 32) != 0)
-        why = FMT == 8 ? "K must be a positive multiple of 16 (16 e4m3 weights per 16-byte load)"
-                       : "K must be a positive multiple of 32 (one E8M0 scale per block of 32 weights)";
-    else if (a.B < 1 || a.B > 4) why = "batch must be 1..4 (more rows take the bf16 lm_head on the dequantised weights)";
-    else if (!a.q || !a.scale || !a.x || !a.out_ids || !a.ws_val || !a.ws_idx)
-        why = "weights, scales, x, out_ids and both workspaces must not be null";
-    if (!why) return 0;
-    snprintf(msg, sizeof(msg), "%s: %s", who, why);
-    spider_set_error(msg);
-    return -1;
+    if (a.V <= 0 || a.K <= 0 || a.K % WQ_LW<FMT> != 0) return wq_fail(who, WQ_K_RULE<FMT>);
+    if (a.B < 1 || a.B > 4) return wq_fail(who, "batch must be 1..4 (more rows take the bf16 lm_head on the dequantised weights)");
+    if (!a.q || !a.scale || !a.x || !a.out_ids || !a.ws_val || !a.ws_idx)
+        return wq_fail(who, "weights, scales, x, out_ids and both workspaces must not be null");
+    return 0;
 }
 
 template <int FMT, bool PROC>
@@ -362,12 +244,8 @@ int lmq_batch(const LmqArgs& a, const LmProc& pr) {
 
 int lmq_proc_make(const char* who, LmProc& pr, const void* seen, const void* ban, const float* penalty, const int* min_new,
                   const int* eos_ids, const int* n_eos, const int* n_hist, int V) {
-    static thread_local char msg[200];
-    if (!(seen && ban && penalty && min_new && eos_ids && n_eos && n_hist)) {
-        snprintf(msg, sizeof(msg), "%s: seen, ban, penalty, min_new, eos_ids, n_eos and n_hist are required", who);
-        spider_set_error(msg);
-        return -1;
-    }
+    if (!(seen && ban && penalty && min_new && eos_ids && n_eos && n_hist))
+        return wq_fail(who, "seen, ban, penalty, min_new, eos_ids, n_eos and n_hist are required");
     pr = LmProc{(const uint32_t*)seen, (const uint32_t*)ban, penalty, min_new, eos_ids, n_eos, n_hist, (V + 31) / 32};
     return 0;
 }

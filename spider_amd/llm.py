@@ -624,14 +624,14 @@ class LlamaEngine:
     # Measured on MI355X, Qwen2.5-7B shapes at context 1536 (scripts/exp/decode_vs_batch.py), ms per decode step by rows 1 / 2 / 3 / 4 / 5 / 8:
     # row-major GEMVs 2.84 / 3.28 / 3.75 / 4.36 (then fragment-major 3.21 / 3.43); fragment-major from 2 rows: 2.99 / 3.09 / 3.16 / 3.23 / 3.43.
     FM_MIN_BATCH = int(os.environ.get("SPIDER_DECODE_FM_MIN", "2"))
-    # weight_dtype="fp8" engines: decode graphs of up to this many rows stream the e4m3 bytes (csrc/gemv_w8.hip, which exists for 1..4
+    # weight_dtype="fp8" engines: decode graphs of up to this many rows stream the e4m3 bytes (csrc/gemv_wq.hip, which exists for 1..4
     # rows), larger ones take the bf16 route above on the dequantised weights. Measured on MI355X, Qwen2.5-7B shapes at context 1536
     # (scripts/exp/fp8_decode_cost.py: both engines alternated in one process, 3 rounds of 96 replays, medians; rounds within 1 us),
     # us per captured decode step by rows 1 / 2 / 3 / 4: bf16 on the route above (row-major at 1, fragment-major from 2)
     # 2638 / 2911 / 2996 / 3063, fp8 1823 / 2162 / 2536 / 3003 = 0.69 / 0.74 / 0.85 / 0.98 of it. 2 % at 4 rows is below the 3 % that
     # counts as a difference, so the range stops at 3.
     FP8_MAX_ROWS = 3
-    # weight_dtype="mxfp4" engines: decode graphs of up to this many rows stream the e2m1 bytes and E8M0 scales (csrc/gemv_w4.hip, which
+    # weight_dtype="mxfp4" engines: decode graphs of up to this many rows stream the e2m1 bytes and E8M0 scales (csrc/gemv_wq.hip, which
     # exists for 1..4 rows). Set by the same rule as FP8_MAX_ROWS from scripts/exp/mxfp4_decode_cost.py: the largest row count at which
     # the MXFP4 step beats the bf16 route of the same row count by >= 3 %. Measured on MI355X, Qwen2.5-7B shapes at context 1536 (the
     # three engines alternated in one process, 3 rounds of 96 replays, medians; rounds within 2 us), us per captured decode step by

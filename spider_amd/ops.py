@@ -280,14 +280,14 @@ def gemv_swiglu(W_gate_up, x, norm_w=None, eps=0.0, out=None):
 
 
 FP8 = torch.float8_e4m3fn      # OCP e4m3fn (448 = 0x7e), the FP8 of gfx950 -- not MI300's e4m3fnuz
-W8_LDS_MAX_DEFAULT = 160 * 1024 - 256  # bytes of staged activations per block (csrc/gemv_w8.hip: W8_LDS_BUDGET_BYTES)
+W8_LDS_MAX_DEFAULT = 160 * 1024 - 256  # bytes of staged activations per block (csrc/wq_common.hpp: WQ_LDS_HW_LIMIT)
 W8_MAX_ROWS = 4                # rows the weight-only FP8 GEMVs exist for
-W8_LDS_MAX = min(int(_os.environ.get("SPIDER_W8_LDS_MAX", "0")) or W8_LDS_MAX_DEFAULT, 160 * 1024 - 256)   # mirror of csrc/gemv_w8.hip
+W8_LDS_MAX = min(int(_os.environ.get("SPIDER_W8_LDS_MAX", "0")) or W8_LDS_MAX_DEFAULT, 160 * 1024 - 256)   # mirror of csrc/wq_common.hpp: wq_lds_max<8>
 
 
 def w8_norm_fits(B: int, K: int) -> bool:
     """True when gemv_w8 / gemv_swiglu_w8 can fuse the RMSNorm for B rows of K: the staged activations (rows padded to whole
-    1024-element chunks) fit the kernel's LDS budget (csrc/gemv_w8.hip: W8_LDS_BUDGET)"""
+    1024-element chunks) fit the kernel's LDS budget (csrc/wq_common.hpp: wq_lds_bytes<8> against wq_lds_max<8>)"""
     return B * ((K + 1023) // 1024) * 2048 <= W8_LDS_MAX
 
 
@@ -335,14 +335,14 @@ def gemv_swiglu_w8(Wq_gate_up, scale, x, norm_w=None, eps=0.0, out=None):
     return out
 
 
-W4_LDS_MAX_DEFAULT = 160 * 1024 - 256  # bytes of staged activations per block (csrc/gemv_w4.hip: W4_LDS_BUDGET_BYTES)
+W4_LDS_MAX_DEFAULT = 160 * 1024 - 256  # bytes of staged activations per block (csrc/wq_common.hpp: WQ_LDS_HW_LIMIT)
 W4_MAX_ROWS = 4                # rows the weight-only MXFP4 GEMVs exist for
-W4_LDS_MAX = min(int(_os.environ.get("SPIDER_W4_LDS_MAX", "0")) or W4_LDS_MAX_DEFAULT, 160 * 1024 - 256)   # mirror of csrc/gemv_w4.hip
+W4_LDS_MAX = min(int(_os.environ.get("SPIDER_W4_LDS_MAX", "0")) or W4_LDS_MAX_DEFAULT, 160 * 1024 - 256)   # mirror of csrc/wq_common.hpp: wq_lds_max<4>
 
 
 def w4_norm_fits(B: int, K: int) -> bool:
     """True when gemv_w4 / gemv_swiglu_w4 can fuse the RMSNorm for B rows of K: the staged activations (rows padded to whole
-    2048-element chunks) fit the kernel's LDS budget (csrc/gemv_w4.hip: W4_LDS_BUDGET)"""
+    2048-element chunks) fit the kernel's LDS budget (csrc/wq_common.hpp: wq_lds_bytes<4> against wq_lds_max<4>)"""
     return B * ((K + 2047) // 2048) * 4096 <= W4_LDS_MAX
 
 

@@ -1,4 +1,4 @@
-"""GPU: the weight-only FP8 decode GEMVs (ops.gemv_w8 / ops.gemv_swiglu_w8, csrc/gemv_w8.hip) against an fp64 restatement on
+"""GPU: the weight-only FP8 decode GEMVs (ops.gemv_w8 / ops.gemv_swiglu_w8, csrc/gemv_wq.hip) against an fp64 restatement on
 W_eff = float(q) * scale that rounds where the kernel rounds.
 
 The bound is derived, not measured (the 1e-2 * std + 1e-2 * |ref| of tests/test_hip_ops.py for the bf16 GEMV is a measured one).

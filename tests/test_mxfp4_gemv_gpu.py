@@ -1,4 +1,4 @@
-"""GPU: the weight-only MXFP4 decode GEMVs (ops.gemv_w4 / ops.gemv_swiglu_w4, csrc/gemv_w4.hip) against an fp64 restatement on
+"""GPU: the weight-only MXFP4 decode GEMVs (ops.gemv_w4 / ops.gemv_swiglu_w4, csrc/gemv_wq.hip) against an fp64 restatement on
 W_eff[n, k] = e2m1(code) * 2^(scales[n, k / 32] - 127) that rounds where the kernel rounds.
 
 The bound is the derived one of tests/test_fp8_gemv_gpu.py, restated for this format. With u = 2^-24 the unit roundoff of fp32:
