@@ -157,6 +157,34 @@ int spider_decode_advance_seen_ngram_i32(const int* next_ids, int* cur_ids, int*
                                          int* n_hist, void* seen, const int* prompt_ids, const int* n_prompt, int pcap,
                                          const int* ngram, const void* ban, void* ban_step, int V, int cap, int B, void* stream);
 
+/* Prompt-lookup decoding (transformers generate(prompt_lookup_num_tokens = K), PromptLookupCandidateGenerator; csrc/spec_decode.hip):
+ * a decode step of ONE greedy sequence carries R = K + 1 rows, the last accepted token and up to K drafted successors.
+ * spider_attn_verify_bf16: spider_attn_decode_bf16 for R consecutive query rows per sequence that share the sequence's cache under
+ *   a causal rule. q [B*R, n_q, d] (rotated by spider_rope_kv_append_bf16 with S = R, which also wrote the R new K / V rows at slot
+ *   ... slot + R - 1), caches [B, n_kv, T_max, d], kv_beg / kv_end [B] (kv_end includes row 0's own token): row r of sequence b sees
+ *   exactly the slots kv_beg[b] <= j < kv_end[b] + r (clamped to T_max). out [B*R, n_q*d]. ws_o: B*R*n_q*nsplit*d floats, ws_ml:
+ *   B*R*n_q*nsplit*2. d = 128, GQA group 1 ... 8, R 1 ... 8; anything else returns -1 with a message.
+ * Row layout of the step's cursors: ids / pos / slot / lm_out int32 [B*R]; n_prompt, n_hist, kv_end, n_draft int32 [B]; prompt_ids
+ *   [B, pcap], hist [B, cap]; ngram (= max_matching_ngram_size, clamped to 0 ... 8) and k_draft (= K, clamped to 0 ... R - 1) int32
+ *   [1], read when the kernel runs (one captured graph serves every value); counters int64 [B, 3] = steps, drafted, accepted.
+ * spider_prompt_lookup_draft_i32: over s = prompt_ids[b, :n_prompt[b]] ++ hist[b, :n_hist[b]] (length L; history slots at or past
+ *   cap read as -1), for n = min(ngram, L - 1) ... 1 the EARLIEST i with s[i : i + n] == s[L - n :] and i + n < L gives the draft
+ *   s[i + n : min(i + n + K, L)]; the first n that has one wins, else n_draft[b] = 0. Writes n_draft[b], ids[r] = draft[r - 1] for
+ *   1 <= r <= n_draft, ids[r] = ids[0] for the other rows r >= 1, pos[r] = pos[0] + r, slot[r] = slot[0] + r. Row 0 is the caller's.
+ * spider_spec_advance_draft_i32: closes a verify step whose arg-max ids are lm_out (lm_out[r] = the token behind row r). a = the
+ *   largest j <= n_draft[b] with lm_out[i - 1] == ids[i] for all 1 <= i <= j; hist gets lm_out[0 .. a] (slots at or past cap are
+ *   dropped), n_hist, kv_end, pos[0], slot[0] += a + 1, counters += (1, n_draft, a), ids[0] = lm_out[a]; then the draft above on
+ *   the advanced sequence. One block per sequence; nothing is written outside the sequence's own rows. */
+int spider_attn_verify_bf16(const void* q, const void* k_cache, const void* v_cache, const int* kv_beg, const int* kv_end,
+                            void* out, void* ws_o, void* ws_ml, int B, int R, int n_q, int n_kv, int d, int T_max, float scale,
+                            int nsplit, void* stream);
+int spider_prompt_lookup_draft_i32(const int* prompt_ids, const int* n_prompt, int pcap, const int* hist, const int* n_hist,
+                                   int cap, const int* ngram, const int* k_draft, int* ids, int* pos, int* slot, int* n_draft,
+                                   int R, int B, void* stream);
+int spider_spec_advance_draft_i32(const int* lm_out, int* ids, int* pos, int* slot, int* kv_end, int* n_draft, int* hist,
+                                  int* n_hist, int cap, const int* prompt_ids, const int* n_prompt, int pcap, const int* ngram,
+                                  const int* k_draft, void* counters, int R, int B, void* stream);
+
 /* Beam search step (transformers GenerationMixin._beam_search: _get_top_k_continuations, _get_running_beams_for_next_iteration and
  * the cache reorder; num_beams / length_penalty reach it from spider.py:1471-1508 and conversation.py:151-173). rows = B * K.
  * spider_beam_partial_bf16: per row of raw bf16 logits [rows, V] and slice of 4096 tokens (nslice = ceil(V / 4096)): ws_ms

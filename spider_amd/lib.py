@@ -65,6 +65,10 @@ SIGNATURES = {
     "spider_rope_kv_append_mrope_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "spider_attn_decode_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "spider_attn_decode_fused_bf16": (_i, [_vp] * 11 + [_i, _i, _i, _i, _i, _f, _i, _vp]),
+    # prompt-lookup decoding (csrc/spec_decode.hip)
+    "spider_attn_verify_bf16": (_i, [_vp] * 8 + [_i] * 6 + [_f, _i, _vp]),
+    "spider_prompt_lookup_draft_i32": (_i, [_vp, _vp, _i, _vp, _vp, _i] + [_vp] * 6 + [_i, _i, _vp]),
+    "spider_spec_advance_draft_i32": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "spider_set_attn_inline": (_i, [_i]),
     "spider_set_attn_xlane": (_i, [_i]),
     "spider_set_gemv_sched": (_i, [_i]),

@@ -29,6 +29,11 @@ finished-hypotheses bookkeeping on the trace the device wrote. num_beams=1 is th
 Sampling (do_sample=True with temperature / top_k 1..64 / top_p / seed, as conversation.py:151-173 calls generate): behind the
 raw-logits lm_head two launches (csrc/sample.hip) apply the processors, keep the top_k best, cut the nucleus and draw with a
 counter-based generator, inside the captured decode graph; `sample_token_host` / `sample_uniform_host` are the definition.
+
+Prompt-lookup decoding (prompt_lookup_num_tokens=K, max_matching_ngram_size=N; one greedy sequence): the decode step runs at K + 1
+rows -- the last accepted token and K tokens drafted from an earlier occurrence of the sequence's last n-gram -- with the R-row
+weight streams, rope_kv_append(S = R) and a verify attention in which row r sees r more cache rows; one launch accepts the agreed
+prefix, appends it and drafts the next step (csrc/spec_decode.hip). `prompt_lookup_draft_host` / `spec_accept_host` are the definition.
 """
 from __future__ import annotations
 
@@ -325,6 +330,84 @@ def process_logits_host(logits: torch.Tensor, seen: torch.Tensor, p: float, ban:
     return lv
 
 
+def prompt_lookup_off(prompt_lookup_num_tokens) -> bool:
+    """None and 0 switch prompt-lookup decoding off, as in transformers; every other value is validated by `resolve_prompt_lookup`"""
+    K = prompt_lookup_num_tokens
+    return K is None or (K == 0 and not isinstance(K, (bool, float)))
+
+
+def resolve_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size=None, B: int = 1, S: int = 0, max_new_tokens: int = 0,
+                          max_len: int = 0, decode_rows: int = 8, head_dim: int = 128, do_sample: bool = False, num_beams=1,
+                          processed: bool = False, no_repeat_ngram_size=None, output_hidden_states: bool = False,
+                          return_logits: bool = False):
+    """Validate `generate(prompt_lookup_num_tokens=K, max_matching_ngram_size=N)` (transformers' prompt-lookup decoding) against what
+    the verify step implements and return (K, N), or None when the keyword is off (None or 0: everything stays as without it, and
+    max_matching_ngram_size is not looked at, as in transformers). K drafts ride as K more rows of the decode step, so K is an int
+    in 1 .. min(decode_rows, ops.SPEC_MAX_ROWS) - 1; N defaults to transformers' 2 and has to lie in 1 .. ops.SPEC_MAX_NGRAM. The served ground is one
+    greedy sequence (batch 1, num_beams 1, do_sample False) without logits processors, no_repeat_ngram_size, output_hidden_states or
+    return_logits, at head_dim 128, with S + max_new_tokens + K <= max_len (a rejected draft still writes its K / V row). Everything
+    else raises and names the argument; nothing is ignored."""
+    K = prompt_lookup_num_tokens
+    if prompt_lookup_off(K):
+        return None
+    rows = min(decode_rows, ops.SPEC_MAX_ROWS)      # of the decode graph, and of the verify kernels
+    if isinstance(K, bool) or not isinstance(K, int) or not (1 <= K <= rows - 1):
+        raise ValueError(f"`prompt_lookup_num_tokens` has to be an integer in [1, {rows - 1}] (the drafts are rows of the "
+                         f"decode graph's {rows}) or None / 0, but is {K}")
+    N = 2 if max_matching_ngram_size is None else max_matching_ngram_size
+    if isinstance(N, bool) or not isinstance(N, int) or not (1 <= N <= ops.SPEC_MAX_NGRAM):
+        raise ValueError(f"`max_matching_ngram_size` has to be an integer in [1, {ops.SPEC_MAX_NGRAM}], but is {N}")
+    if B != 1:
+        raise NotImplementedError(f"prompt_lookup_num_tokens serves one sequence per call (transformers' assisted decoding is batch 1 too), "
+                                  f"but the batch has {B} rows")
+    if do_sample:
+        raise NotImplementedError("prompt_lookup_num_tokens with do_sample=True is not implemented (speculative sampling needs the rejection rule)")
+    if num_beams != 1:
+        raise NotImplementedError("prompt_lookup_num_tokens with num_beams > 1 is not implemented")
+    if no_repeat_ngram_size:
+        raise NotImplementedError("prompt_lookup_num_tokens with no_repeat_ngram_size is not implemented: pass None or 0")
+    if processed:
+        raise NotImplementedError("prompt_lookup_num_tokens with repetition_penalty / min_length / min_new_tokens / suppress_tokens / "
+                                  "bad_words_ids is not implemented: pass their neutral values")
+    if output_hidden_states:
+        raise NotImplementedError("prompt_lookup_num_tokens with output_hidden_states is not implemented")
+    if return_logits:
+        raise NotImplementedError("prompt_lookup_num_tokens with return_logits is not implemented")
+    if head_dim != 128:
+        raise NotImplementedError(f"prompt_lookup_num_tokens needs head_dim 128 (the verify attention), but head_dim is {head_dim}")
+    if S + max_new_tokens + K > max_len:
+        raise ValueError(f"prompt_lookup_num_tokens={K}: prompt {S} + max_new_tokens {max_new_tokens} + {K} draft rows exceed the "
+                         f"engine's max_len={max_len} (a rejected draft still writes its K / V row)")
+    return K, N
+
+
+def prompt_lookup_draft_host(seq: Sequence[int], K: int, N: int) -> List[int]:
+    """The draft of transformers' PromptLookupCandidateGenerator(num_output_tokens=K, max_matching_ngram_size=N) behind the sequence
+    seq = s[0..L), with logits_processor=None, no EOS cut and max_length far away: for n = min(N, L - 1) .. 1 the EARLIEST i with
+    s[i : i + n] == s[L - n :] and i + n < L gives s[i + n : min(i + n + K, L)]; the first n that has one wins, else []. seq is the
+    row's input_ids (pads included) followed by its generated tokens; the generated tokens alone for an inputs_embeds call."""
+    s = [int(t) for t in seq]
+    L, K, N = len(s), int(K), int(N)
+    if K < 1:
+        return []
+    for n in range(min(N, L - 1), 0, -1):
+        tail = s[L - n:]
+        for i in range(L - n):
+            if s[i:i + n] == tail:
+                return s[i + n:min(i + n + K, L)]
+    return []
+
+
+def spec_accept_host(ids: Sequence[int], n_draft: int, lm_out: Sequence[int]) -> int:
+    """The number of drafts a verify step accepts: ids[0] is the last accepted token, ids[1 .. n_draft] its drafted successors and
+    lm_out[r] the model's greedy token behind row r; a = the largest j <= n_draft with lm_out[i - 1] == ids[i] for all 1 <= i <= j.
+    The sequence then grows by lm_out[0 .. a]: the a agreed drafts and the model's own token behind the last of them."""
+    a = 0
+    while a < int(n_draft) and int(lm_out[a]) == int(ids[a + 1]):
+        a += 1
+    return a
+
+
 SAMPLE_MAX_K = 64       # top_k limit of the sampling kernels (csrc/sample.hip)
 
 
@@ -594,11 +677,12 @@ class _PrefillHandle:
 
 
 class GenerateOutput:
-    def __init__(self, sequences, hidden_states=None, sequences_scores=None, beam_indices=None):
+    def __init__(self, sequences, hidden_states=None, sequences_scores=None, beam_indices=None, prompt_lookup=None):
         self.sequences = sequences
         self.hidden_states = hidden_states
         self.sequences_scores = sequences_scores     # beam search only (num_beams > 1)
         self.beam_indices = beam_indices
+        self.prompt_lookup = prompt_lookup           # prompt_lookup_num_tokens only: dict(steps=, drafted=, accepted=)
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -844,6 +928,7 @@ class LlamaEngine:
         self.cos_sin = rope_table(c, max(c.max_pos, T)).to(dv)
         self._graphs = {}
         self._beam_kv_tmp = {}      # cache set -> second K / V buffer of the beam-search reorder (allocated by the first beam request)
+        self.last_prompt_lookup = None      # dict(steps=, drafted=, accepted=) of the last decode_finish when it was a prompt-lookup request, else None
 
     def _kv(self, cache_set: int):
         while len(self._kv_sets) <= cache_set:
@@ -906,12 +991,15 @@ class LlamaEngine:
 
     @staticmethod
     def _state_key(B: int, output_hidden_states: bool, return_logits: bool, cache_set: int, processed: bool = False,
-                   beam: Optional[tuple] = None, sample: bool = False, ngram: bool = False) -> tuple:
+                   beam: Optional[tuple] = None, sample: bool = False, ngram: bool = False, lookup: int = 0) -> tuple:
         """key of a decode state + captured graph; requests with logits processors have their own (one more element), and so have
         beam-search requests (B = batch rows; beam = (num_beams, continuations kept per step): three more elements), sampling
-        requests ("sample", behind the processors' element) and requests with no_repeat_ngram_size ("ngram" as the last element;
-        they are processed requests)"""
+        requests ("sample", behind the processors' element), requests with no_repeat_ngram_size ("ngram" as the last element;
+        they are processed requests) and prompt-lookup requests (lookup = K > 0 drafts: "lookup" and the K + 1 rows of the step;
+        one graph serves every max_matching_ngram_size)"""
         key = (int(B), bool(output_hidden_states), bool(return_logits), int(cache_set))
+        if lookup:
+            return key + ("lookup", int(lookup) + 1)
         if beam is not None:
             return key + ("beam", int(beam[0]), int(beam[1]))
         key = key + (True,) if (processed or ngram) else key
@@ -920,15 +1008,16 @@ class LlamaEngine:
 
     def would_capture(self, B: int, output_hidden_states: bool = False, return_logits: bool = False, cache_set: int = 0,
                       processed: bool = False, num_beams: int = 1, n_eos: int = 0, do_sample: bool = False,
-                      no_repeat_ngram: bool = False) -> bool:
+                      no_repeat_ngram: bool = False, prompt_lookup_num_tokens: Optional[int] = None) -> bool:
         """True when the decode loop of such a request would capture its hipGraph (state missing or not captured yet).
         processed: a request with non-neutral logits processors (repetition_penalty != 1, a ban set, or EOS banned at first)
         num_beams > 1: a beam-search request of B batch rows with n_eos EOS ids (they size the continuations kept per step)
         do_sample: a sampling request (one graph serves every temperature / top_k / top_p / seed)
-        no_repeat_ngram: a request with no_repeat_ngram_size > 0 (one graph serves every size)"""
+        no_repeat_ngram: a request with no_repeat_ngram_size > 0 (one graph serves every size)
+        prompt_lookup_num_tokens: a prompt-lookup request of that many drafts (one graph per K serves every max_matching_ngram_size)"""
         beam = (num_beams, max(2, 1 + n_eos) * num_beams) if num_beams > 1 else None
         ent = self._graphs.get(self._state_key(B, output_hidden_states, return_logits, cache_set, processed, beam, bool(do_sample),
-                                               bool(no_repeat_ngram)))
+                                               bool(no_repeat_ngram), int(prompt_lookup_num_tokens or 0)))
         return ent is None or ent[1] is None
 
     def _vocab_changed(self):
@@ -987,6 +1076,7 @@ class LlamaEngine:
         # batched_weight_stream engines: above those ranges, up to *_FM_MAX_ROWS rows, the same bytes in fragment-major order (csrc/gemv_qfm.hip)
         q8fm = self.batched_weight_stream and self.weight_dtype == "fp8" and not w8 and B <= min(self.FP8_FM_MAX_ROWS, ops.QFM_MAX_ROWS)
         q4fm = self.batched_weight_stream and self.weight_dtype == "mxfp4" and not w4 and B <= min(self.MXFP4_FM_MAX_ROWS, ops.QFM_MAX_ROWS)
+        lookup = st.get("lookup")       # prompt-lookup verify step: the layer loop below at B = R rows, attention under the causal rule
         for l, lw in enumerate(self.layers):
             if q8fm:
                 ops.gemv_fm_w8(lw["w_qkv_q8fm"], lw["w_qkv_s8"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), lw["w_qkv"].shape[0],
@@ -1008,7 +1098,12 @@ class LlamaEngine:
                 ops.gemv_fm(lw["w_qkv_fm"], h, lw["w_qkv"].shape[0], bias=lw["b_qkv"], out=st["qkv"], norm_eps=c.eps)
             else:
                 ops.gemv(lw["w_qkv"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), bias=lw["b_qkv"], out=st["qkv"])
-            if c.head_dim == 128:   # RoPE + KV append + split-KV attention + combine: one launch
+            if lookup is not None:  # the B rows are ONE sequence's token and its drafts: R appended K / V rows, row r sees r more of them
+                ops.rope_kv_append(st["qkv"], st["pos"], st["slot"], self.cos_sin, st["q"], k_cache[l], v_cache[l],
+                                   1, B, c.n_q, c.n_kv, c.head_dim)
+                ops.attn_verify(st["q"], k_cache[l], v_cache[l], st["kv_end"], B, kv_beg=st["kv_beg"], nsplit=st["nsplit"],
+                                ws=st["attn_ws"], out=st["attn"])
+            elif c.head_dim == 128:   # RoPE + KV append + split-KV attention + combine: one launch
                 ops.attn_decode_fused(st["qkv"], st["pos"], self.cos_sin, k_cache[l], v_cache[l], st["kv_end"],
                                       st["kv_beg"], st["attn_cnt"], c.n_q, st["nsplit"], st["attn_ws"], st["attn"])
             else:
@@ -1051,6 +1146,10 @@ class LlamaEngine:
                 h = ops.gemv(lw["w_down"], st["act"], res=h1, out=st["h2"][l & 1])
             if hs is not None:
                 hs[l + 1].copy_(h)
+        if lookup is not None:      # the model's token behind every row, then accept / append / advance / draft in one launch
+            self._lm_head_step(st, h, st["next_ids"], None, None, fm)
+            ops.spec_advance_draft(lookup, st["hist"], st["n_hist"])
+            return
         if st.get("beam") is not None:      # beam search: the raw logits of the B * K rows go to the beam step instead of an arg-max
             self._lm_head_step(st, h, st["beam"]["lm_ids"], st["logits"], None, fm)
             self._beam_step(st)
@@ -1172,6 +1271,21 @@ class LlamaEngine:
                               kv_tmp=self._beam_kv_tmp[cache_set])
         return st
 
+    def _make_lookup_state(self, R: int, cache_set: int = 0) -> dict:
+        """decode state of a prompt-lookup request: the activations and step cursors (cur_ids = the rows' input ids, next_ids = the
+        model's token behind every row, pos, slot) of R = K + 1 rows, the cache cursors and token history of ONE sequence, and under
+        "lookup" the buffers of ops.spec_advance_draft / ops.prompt_lookup_draft"""
+        st = self._make_state(R, False, False, cache_set)
+        dv = self.device
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dv)
+        st.update(kv_end=i32(1), kv_beg=i32(1), hist=i32(1, self.max_len), n_hist=i32(1), first=i32(1))
+        st["lookup"] = dict(prompt_ids=i32(1, self.max_len), n_prompt=i32(1), ngram=i32(1), k_draft=i32(1), n_draft=i32(1),
+                            counters=torch.zeros(1, 3, dtype=torch.int64, device=dv), ids=st["cur_ids"], pos=st["pos"],
+                            slot=st["slot"], lm_out=st["next_ids"], kv_end=st["kv_end"])
+        return st
+
+    _LOOKUP_BUFS = ("prompt_ids", "n_prompt", "ngram", "k_draft", "n_draft", "counters")
+
     # ------------------------------------------------------------------ public generate
     @torch.no_grad()
     def generate(self, input_ids: Optional[torch.Tensor] = None, inputs_embeds: Optional[torch.Tensor] = None, **kw):
@@ -1189,7 +1303,8 @@ class LlamaEngine:
                       position_ids: Optional[torch.Tensor] = None, cache_set: int = 0, repetition_penalty=1.0, min_length=0,
                       min_new_tokens=0, suppress_tokens=None, bad_words_ids=None, length_penalty=1.0, early_stopping=False,
                       num_return_sequences=1, num_beam_groups=1, constraints=None, force_words_ids=None, temperature=1.0,
-                      top_k=None, top_p=1.0, seed=None, no_repeat_ngram_size=None, _whole_generate=False, _row0=0, **unused):
+                      top_k=None, top_p=1.0, seed=None, no_repeat_ngram_size=None, prompt_lookup_num_tokens=None,
+                      max_matching_ngram_size=None, _whole_generate=False, _row0=0, **unused):
         """First half of `generate`: the prompt pass (KV cache of `cache_set` filled, first token chosen, decode cursors set), all
         ENQUEUED on the current stream without a host sync; returns a handle for `decode_finish`. Two requests can be in flight on
         two streams when they use different cache sets (prefill of one beside the decode loop of the other: SpiderFreeInfer's
@@ -1229,7 +1344,15 @@ class LlamaEngine:
         (`sample_token_host` is the definition; `resolve_sampling` the accepted ground: top_k 1..64, None = HF's default). Keyword
         arguments only. The token of row r at step n depends on (seed, r, n) and the logits alone -- not on graph / eager,
         sync_every, the split path, the cache set or the grouping of more than 8 rows. seed=None draws the seed from torch's default
-        CPU generator (torch.manual_seed makes the call reproducible). do_sample=False ignores the three warper arguments."""
+        CPU generator (torch.manual_seed makes the call reproducible). do_sample=False ignores the three warper arguments.
+        prompt_lookup_num_tokens=K (an int 1..7; None / 0 = off) with max_matching_ngram_size=N (1..8, default 2): transformers'
+        prompt-lookup decoding for one greedy sequence (`resolve_prompt_lookup` is the served ground). Every decode step carries the
+        last accepted token and up to K tokens drafted from an earlier occurrence of the sequence's last n-gram
+        (`prompt_lookup_draft_host`; the sequence is the input_ids row + generated tokens, the generated tokens alone for
+        inputs_embeds) as K + 1 rows of the weight streams, verifies them in one pass (csrc/spec_decode.hip) and keeps the prefix the
+        model agrees with plus the model's own next token (`spec_accept_host`): 1 .. K + 1 tokens per step, and the sequence is the
+        greedy one. A state and graph of its own per K. The counters dict(steps=, drafted=, accepted=) of the call are
+        `GenerateOutput.prompt_lookup` and `last_prompt_lookup`; with sync_every > 1 they include the steps that ran past the stop."""
         sampling = resolve_sampling(do_sample, temperature, top_k, top_p, num_return_sequences) if num_beams == 1 else None
         ngram = resolve_no_repeat_ngram(no_repeat_ngram_size)
         if sampling is not None:
@@ -1245,6 +1368,13 @@ class LlamaEngine:
         if max_new_tokens is None:   # HF: generation_config.max_new_tokens, else max_length (default 20) counts the prompt
             max_new_tokens = gc.get("max_new_tokens") or max(1, int(gc.get("max_length", 20)) - (0 if embeds_only else S_in))
         B_all = inputs_embeds.shape[0] if embeds_only else input_ids.shape[0]
+        lookup = None       # (K, N) of a prompt-lookup request
+        if not prompt_lookup_off(prompt_lookup_num_tokens):
+            pen, min_new, ban = resolve_logits_processors(S_in, _id_list(eos_token_id), repetition_penalty, min_length, min_new_tokens,
+                                                          suppress_tokens, bad_words_ids)
+            lookup = resolve_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size, B_all, S_in, max_new_tokens, self.max_len,
+                                           self.DECODE_ROWS, c.head_dim, bool(do_sample), num_beams,
+                                           pen != 1.0 or min_new > 0 or bool(ban), ngram, output_hidden_states, return_logits)
         beam = None
         if num_beams != 1 and not _whole_generate:
             raise NotImplementedError("num_beams > 1 runs through LlamaEngine.generate only: the split prefill_begin / adopt / decode_finish "
@@ -1307,6 +1437,11 @@ class LlamaEngine:
             return self._beam_decode(beam, h.view(B, S, -1)[:, -1], next_pos, kv_beg, B, S, None if embeds_only else input_ids,
                                      max_new_tokens, eos_l, pad_token_id, float(length_penalty), early_stopping, num_return_sequences,
                                      return_dict_in_generate, use_graph, max(1, int(sync_every)), return_logits, cache_set)
+
+        if lookup is not None:
+            return self._lookup_begin(lookup, h.view(B, S, -1)[:, -1].contiguous(), next_pos, kv_beg, S, embeds_only, input_ids,
+                                      max_new_tokens, stopping_criteria, eos_token_id, pad_token_id, return_dict_in_generate,
+                                      use_graph, sync_every, cache_set)
 
         # decode state (static buffers + captured hipGraph) is cached per (batch, outputs): repeated generate() calls
         # replay the same graph instead of re-capturing ~200 launches
@@ -1380,6 +1515,39 @@ class LlamaEngine:
                               use_graph=use_graph, sync_every=sync_every, return_logits=return_logits, hidden_steps=hidden_steps,
                               logits_steps=logits_steps, tokens=tokens)
 
+    def _lookup_begin(self, lookup, last, next_pos, kv_beg, S, embeds_only, input_ids, max_new_tokens, stopping_criteria,
+                      eos_token_id, pad_token_id, return_dict_in_generate, use_graph, sync_every, cache_set) -> "_PrefillHandle":
+        """Behind the prompt pass of a prompt-lookup request (one sequence; `last` [1, H] is its final residual at the last position):
+        the first token, the cursors of row 0, this request's K / N and prompt ids in the state's buffers, and the draft of the first
+        verify step -- all enqueued, no host sync."""
+        c = self.cfg
+        K, N = lookup
+        skey = self._state_key(1, False, False, cache_set, lookup=K)
+        if skey not in self._graphs:
+            self._graphs[skey] = [self._make_lookup_state(K + 1, cache_set), None]
+        st = self._graphs[skey][0]
+        lk = st["lookup"]
+        st["kv_beg"].copy_(kv_beg)
+        ops.lm_head_argmax(self.lm_head, last, norm_w=self.norm, eps=c.eps, out_ids=st["first"], ws=st["lm_ws"])
+        st["cur_ids"][:1].copy_(st["first"])
+        st["pos"][:1].copy_(next_pos)
+        st["slot"][:1].fill_(S)
+        st["kv_end"].fill_(S + 1)
+        st["hist"][:, :1].copy_(st["first"].view(1, 1))
+        st["n_hist"].fill_(1)
+        lk["ngram"].fill_(N)
+        lk["k_draft"].fill_(K)
+        lk["counters"].zero_()
+        lk["n_prompt"].fill_(0 if embeds_only else S)       # with inputs_embeds only, the lookup runs over the generated tokens alone
+        if not embeds_only:
+            lk["prompt_ids"][:, :S].copy_(input_ids)
+        ops.prompt_lookup_draft(lk, st["hist"], st["n_hist"])
+        return _PrefillHandle(B=1, S=S, st=st, skey=skey, embeds_only=embeds_only, input_ids=input_ids, max_new_tokens=max_new_tokens,
+                              stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                              output_hidden_states=False, return_dict_in_generate=return_dict_in_generate, use_graph=use_graph,
+                              sync_every=sync_every, return_logits=False, hidden_steps=None, logits_steps=None,
+                              tokens=st["hist"][:, :max_new_tokens], lookup=lookup)
+
     @torch.no_grad()
     def adopt(self, hd: "_PrefillHandle", cache_set: int = 0) -> "_PrefillHandle":
         """Move a prefilled request into KV cache set `cache_set` (device copies of the prompt's K / V rows and of the decode cursors,
@@ -1391,6 +1559,22 @@ class LlamaEngine:
         if src == cache_set:
             return hd
         B, S = hd.B, hd.S
+        if getattr(hd, "lookup", None) is not None:     # a prompt-lookup request: its row-0 cursors, drafted rows and lookup buffers
+            skey = self._state_key(1, False, False, cache_set, lookup=hd.lookup[0])
+            if skey not in self._graphs:
+                self._graphs[skey] = [self._make_lookup_state(hd.lookup[0] + 1, cache_set), None]
+            dst, st = self._graphs[skey][0], hd.st
+            (ks, vs), (kd, vd) = self._kv(src), self._kv(cache_set)
+            kd[:, :1, :, :S + 1].copy_(ks[:, :1, :, :S + 1])
+            vd[:, :1, :, :S + 1].copy_(vs[:, :1, :, :S + 1])
+            for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "kv_beg", "n_hist", "first"):
+                dst[k].copy_(st[k])
+            for k in self._LOOKUP_BUFS:
+                dst["lookup"][k].copy_(st["lookup"][k])
+            dst["hist"][:, :1].copy_(st["hist"][:, :1])
+            nd = _PrefillHandle(**hd.__dict__)
+            nd.st, nd.skey, nd.tokens = dst, skey, dst["hist"][:, :hd.max_new_tokens]
+            return nd
         processed, sample, ngram = hd.skey[4:5] == (True,), "sample" in hd.skey[4:], "ngram" in hd.skey[4:]
         skey = self._state_key(B, hd.output_hidden_states, hd.return_logits, cache_set, processed, None, sample, ngram)
         if skey not in self._graphs:
@@ -1426,6 +1610,7 @@ class LlamaEngine:
         prompt_cpu = None if embeds_only else input_ids.cpu().long()
         need_check = bool(eos) or bool(stopping_criteria)
         final = None      # (padded tokens [B, k] on the host, k) once a stop condition has been met
+        lookup = getattr(hd, "lookup", None)    # (K, N) of a prompt-lookup request
 
         def check(n_done: int, already: int):
             if not need_check:
@@ -1441,6 +1626,8 @@ class LlamaEngine:
         if use_graph and graph is None and final is None and max_new_tokens > 2:
             # warm the kernels outside capture, then capture one decode step; cursors live on device
             snap = {k: st[k].clone() for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "n_hist", "seen", "ban_step") if k in st}
+            if lookup is not None:      # (the warm-up step's history entries and K / V rows lie past the cursors and are written again)
+                snap_lk = {k: st["lookup"][k].clone() for k in ("n_draft", "counters")}
             s = torch.cuda.Stream(device=dv)
             s.wait_stream(torch.cuda.current_stream(dv))
             with torch.cuda.stream(s):
@@ -1453,7 +1640,25 @@ class LlamaEngine:
                 self._decode_step(st)
             for k, v in snap.items():   # capture does not execute; restore is a no-op safety net
                 st[k].copy_(v)
+            if lookup is not None:
+                for k, v in snap_lk.items():
+                    st["lookup"][k].copy_(v)
             self._graphs[skey][1] = graph
+        while lookup is not None and n < max_new_tokens and final is None:
+            # prompt lookup: every verify step yields 1 .. K + 1 tokens, so `sync_every` steps (at most one per token still wanted) run
+            # before the host reads how many there are; the stop checks then look at every new length, as on the path below.
+            # The cache bounds them too: the host knows n tokens, step j of the block may start from n + j (K + 1) and writes K / V
+            # rows up to slot S + n + j (K + 1) + K - 1, which has to stay below max_len (resolve_prompt_lookup admits j = 0).
+            K = lookup[0]
+            fit = (self.max_len - S - n - K) // (K + 1) + 1
+            for _ in range(max(1, min(int(sync_every), max_new_tokens - n, fit))):
+                if graph is not None:
+                    graph.replay()
+                else:
+                    self._decode_step(st)
+            n = min(int(st["n_hist"].item()), max_new_tokens)
+            final = check(n, checked)
+            checked = n
         while n < max_new_tokens and final is None:
             if graph is not None:
                 graph.replay()
@@ -1481,6 +1686,10 @@ class LlamaEngine:
         out = GenerateOutput(seqs, tuple(hidden_steps) if output_hidden_states else None)
         if return_logits:
             out.logits = torch.stack(logits_steps, 1)
+        self.last_prompt_lookup = None      # the record of the LAST call: a plain request has none
+        if lookup is not None:      # the device's counters of this call (steps that ran past a stop included)
+            steps, drafted, accepted = (int(x) for x in st["lookup"]["counters"][0].tolist())
+            out.prompt_lookup = self.last_prompt_lookup = dict(steps=steps, drafted=drafted, accepted=accepted)
         return out if return_dict_in_generate else seqs
 
     def _beam_decode(self, beam, last, next_pos, kv_beg, B, S, input_ids, max_new_tokens, eos, pad, length_penalty, early_stopping,

@@ -974,6 +974,82 @@ def attn_decode_fused(qkv, pos, cos_sin, k_cache, v_cache, kv_end, kv_beg, count
     return out
 
 
+# --------------------------------------------------------------------------- prompt-lookup decoding (csrc/spec_decode.hip)
+SPEC_MAX_ROWS = 8       # rows per sequence of a verify step (the decode graph's 8 rows)
+SPEC_MAX_NGRAM = 8      # largest max_matching_ngram_size the draft kernel compares
+
+
+def attn_verify(q, k_cache, v_cache, kv_end, R, kv_beg=None, nsplit=1, ws=None, out=None, scale=None):
+    """attn_decode for R consecutive query rows per sequence: q [B * R, n_q, d] (rotated by rope_kv_append with S = R, which also
+    appended the R new K / V rows), kv_end / kv_beg [B]; row r of sequence b sees the slots kv_beg[b] <= j < kv_end[b] + r.
+    Returns out [B * R, n_q * d]."""
+    _chk(q, BF16, "q"); _chk(k_cache, BF16, "k_cache"); _chk(v_cache, BF16, "v_cache"); _chk(kv_end, torch.int32, "kv_end")
+    rows, n_q, d = q.shape
+    B = kv_end.numel()
+    n_kv, T_max = k_cache.shape[1], k_cache.shape[2]
+    if not (isinstance(R, int) and 1 <= R <= SPEC_MAX_ROWS) or rows != B * R:
+        raise ValueError(f"attn_verify: R has to be 1 ... {SPEC_MAX_ROWS} with q [B * R, n_q, d]; got R={R}, {rows} rows, B={B}")
+    assert k_cache.shape[0] >= B and v_cache.shape == k_cache.shape and k_cache.shape[3] == d
+    if kv_beg is not None:
+        _chk(kv_beg, torch.int32, "kv_beg")
+        assert kv_beg.numel() == B
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    if out is None:
+        out = torch.empty(rows, n_q * d, dtype=BF16, device=q.device)
+    else:
+        _chk(out, BF16, "out")
+        assert out.numel() == rows * n_q * d
+    if nsplit > 1:
+        if ws is None:
+            ws = (torch.empty(rows * n_q * nsplit * d, dtype=torch.float32, device=q.device),
+                  torch.empty(rows * n_q * nsplit * 2, dtype=torch.float32, device=q.device))
+        assert ws[0].numel() >= rows * n_q * nsplit * d and ws[1].numel() >= rows * n_q * nsplit * 2, "attn_verify: workspace too small"
+    _lib.call("spider_attn_verify_bf16", _p(q), _p(k_cache), _p(v_cache), _p(kv_beg), _p(kv_end), _p(out),
+              _p(ws[0]) if ws else None, _p(ws[1]) if ws else None, B, R, n_q, n_kv, d, T_max, float(scale), nsplit, _stream())
+    return out
+
+
+def _spec_args(sp: dict, hist, n_hist, advance: bool):
+    """The buffers of a prompt-lookup step: sp = dict(prompt_ids int32 [B, pcap], n_prompt [B], ngram [1], k_draft [1], ids / pos /
+    slot [B * R], n_draft [B]; with `advance` also lm_out [B * R], kv_end [B] and counters int64 [B, 3]); hist int32 [B, cap],
+    n_hist [B]. Returns (B, R)."""
+    for k in ("prompt_ids", "n_prompt", "ngram", "k_draft", "ids", "pos", "slot", "n_draft") + (("lm_out", "kv_end") if advance else ()):
+        _chk(sp[k], torch.int32, k)
+    _chk(hist, torch.int32, "hist"); _chk(n_hist, torch.int32, "n_hist")
+    B = n_hist.numel()
+    assert hist.dim() == 2 and hist.shape[0] == B and hist.shape[1] > 0
+    assert sp["prompt_ids"].dim() == 2 and sp["prompt_ids"].shape[0] == B and sp["prompt_ids"].shape[1] > 0
+    assert sp["n_prompt"].numel() == B and sp["n_draft"].numel() == B and sp["ngram"].numel() >= 1 and sp["k_draft"].numel() >= 1
+    rows = sp["ids"].numel()
+    R = rows // B
+    if rows != B * R or not 1 <= R <= SPEC_MAX_ROWS:
+        raise ValueError(f"prompt lookup: ids has to hold 1 ... {SPEC_MAX_ROWS} rows for each of the {B} sequences, got {rows}")
+    assert sp["pos"].numel() == rows and sp["slot"].numel() == rows
+    if advance:
+        _chk(sp["counters"], torch.int64, "counters")
+        assert sp["lm_out"].numel() == rows and sp["kv_end"].numel() == B and sp["counters"].numel() == B * 3
+    return B, R
+
+
+def prompt_lookup_draft(sp: dict, hist, n_hist):
+    """Draft the rows 1 ... R - 1 of a verify step from the sequence prompt_ids[b, :n_prompt[b]] ++ hist[b, :n_hist[b]]
+    (`llm.prompt_lookup_draft_host` is the definition; buffers: `_spec_args`); row 0 of ids / pos / slot is the caller's."""
+    B, R = _spec_args(sp, hist, n_hist, False)
+    _lib.call("spider_prompt_lookup_draft_i32", _p(sp["prompt_ids"]), _p(sp["n_prompt"]), sp["prompt_ids"].shape[1], _p(hist),
+              _p(n_hist), hist.shape[1], _p(sp["ngram"]), _p(sp["k_draft"]), _p(sp["ids"]), _p(sp["pos"]), _p(sp["slot"]),
+              _p(sp["n_draft"]), R, B, _stream())
+
+
+def spec_advance_draft(sp: dict, hist, n_hist):
+    """Close a verify step (accept the drafts sp['lm_out'] agrees with -- `llm.spec_accept_host` --, append them to hist, advance
+    the cursors, count) and draft the next one, in one launch."""
+    B, R = _spec_args(sp, hist, n_hist, True)
+    _lib.call("spider_spec_advance_draft_i32", _p(sp["lm_out"]), _p(sp["ids"]), _p(sp["pos"]), _p(sp["slot"]), _p(sp["kv_end"]),
+              _p(sp["n_draft"]), _p(hist), _p(n_hist), hist.shape[1], _p(sp["prompt_ids"]), _p(sp["n_prompt"]),
+              sp["prompt_ids"].shape[1], _p(sp["ngram"]), _p(sp["k_draft"]), _p(sp["counters"]), R, B, _stream())
+
+
 # --------------------------------------------------------------------------- GEMM / conv / attention
 def gemm(A, W, bias=None, res=None, rowbias=None, rows_per_group=0, act=None, out_scale=1.0, out=None, out_f32=False,
          res32=None, want32=False):

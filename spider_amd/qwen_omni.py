@@ -710,8 +710,9 @@ class QwenOmniThinker:
         """Returns [B, S + new] token ids like GenerationMixin.generate with input_ids. Length and EOS default to the
         checkpoint's generation config as in the reference's bare `model.generate(**inputs, spk=..., use_audio_in_video=True)`
         (qwen2.5omni_spider_web.py:468): finished rows are pad-filled, the call ends when every row has emitted EOS.
-        = `prefill_begin` + `decode_finish` back to back. do_sample / temperature / top_k / top_p / seed and the logits-processor
-        keywords go to LlamaEngine.prefill_begin as given."""
+        = `prefill_begin` + `decode_finish` back to back. do_sample / temperature / top_k / top_p / seed, the logits-processor
+        keywords and prompt_lookup_num_tokens / max_matching_ngram_size go to LlamaEngine.prefill_begin as given (the prompt-lookup
+        counters: `GenerateOutput.prompt_lookup` with return_dict_in_generate, else `self.llm.last_prompt_lookup`)."""
         return self.decode_finish(self.prefill_begin(input_ids, attention_mask, max_new_tokens, thinker_max_new_tokens, **kw))
 
     @torch.no_grad()
@@ -768,8 +769,10 @@ class QwenOmniThinker:
         # logits-processor keywords select the processed decode graph (LlamaEngine.prefill_begin); min_length alone does so only when
         # it exceeds the spliced prompt length, which is not known here: then either graph missing counts
         # do_sample selects the sampling graph (temperature / top_k / top_p / seed are values the one graph reads)
+        # prompt_lookup_num_tokens selects the verify graph of that many drafts
         wc = lambda processed: self.llm.would_capture(B, output_hidden_states, return_logits, cache_set, processed=processed,
-                                                      do_sample=bool(kw.get("do_sample")))
+                                                      do_sample=bool(kw.get("do_sample")),
+                                                      prompt_lookup_num_tokens=kw.get("prompt_lookup_num_tokens"))
         if kw.get("repetition_penalty") not in (None, 1, 1.0) or kw.get("suppress_tokens") or kw.get("bad_words_ids") \
                 or kw.get("min_new_tokens"):
             return wc(True)

@@ -220,6 +220,50 @@ def _(next_ids, cur_ids, pos, slot, kv_end, hist, n_hist, seen, prompt_ids, n_pr
     return None
 
 
+# ------------------------------------------------------------------------------------------ prompt-lookup decoding
+@_op("attn_verify")
+def attn_verify(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_end: torch.Tensor, rows_per_seq: int,
+                kv_beg: Optional[torch.Tensor] = None, nsplit: int = 1) -> torch.Tensor:
+    """R = rows_per_seq consecutive query rows per sequence against the sequence's KV cache; row r sees the slots
+    kv_beg[b] <= j < kv_end[b] + r. q [B * R, n_q, d] -> [B * R, n_q * d]"""
+    return ops.attn_verify(q.contiguous(), k_cache, v_cache, kv_end, rows_per_seq, kv_beg=kv_beg, nsplit=nsplit)
+
+
+@attn_verify.register_fake
+def _(q, k_cache, v_cache, kv_end, rows_per_seq, kv_beg=None, nsplit=1):
+    return q.new_empty(q.shape[0], q.shape[1] * q.shape[2])
+
+
+@_op("prompt_lookup_draft_", mutates=("ids", "pos", "slot", "n_draft"))
+def prompt_lookup_draft_(prompt_ids: torch.Tensor, n_prompt: torch.Tensor, hist: torch.Tensor, n_hist: torch.Tensor,
+                         ngram: torch.Tensor, k_draft: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor,
+                         n_draft: torch.Tensor) -> None:
+    """prompt-lookup draft (transformers PromptLookupCandidateGenerator) of rows 1 ... R - 1 of a verify step from
+    prompt_ids[b, :n_prompt[b]] ++ hist[b, :n_hist[b]]; ids / pos / slot int32 [B * R], row 0 is the caller's"""
+    ops.prompt_lookup_draft(dict(prompt_ids=prompt_ids, n_prompt=n_prompt, ngram=ngram, k_draft=k_draft, ids=ids, pos=pos, slot=slot,
+                                 n_draft=n_draft), hist, n_hist)
+
+
+@prompt_lookup_draft_.register_fake
+def _(prompt_ids, n_prompt, hist, n_hist, ngram, k_draft, ids, pos, slot, n_draft):
+    return None
+
+
+@_op("spec_advance_draft_", mutates=("ids", "pos", "slot", "kv_end", "n_draft", "hist", "n_hist", "counters"))
+def spec_advance_draft_(lm_out: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, kv_end: torch.Tensor,
+                        n_draft: torch.Tensor, hist: torch.Tensor, n_hist: torch.Tensor, prompt_ids: torch.Tensor,
+                        n_prompt: torch.Tensor, ngram: torch.Tensor, k_draft: torch.Tensor, counters: torch.Tensor) -> None:
+    """end of a verify step: the drafts lm_out agrees with are accepted and appended to hist, the cursors advance, counters
+    int64 [B, 3] += (1, drafted, accepted), and the next step's rows are drafted -- one launch"""
+    ops.spec_advance_draft(dict(prompt_ids=prompt_ids, n_prompt=n_prompt, ngram=ngram, k_draft=k_draft, ids=ids, pos=pos, slot=slot,
+                                n_draft=n_draft, lm_out=lm_out, kv_end=kv_end, counters=counters), hist, n_hist)
+
+
+@spec_advance_draft_.register_fake
+def _(lm_out, ids, pos, slot, kv_end, n_draft, hist, n_hist, prompt_ids, n_prompt, ngram, k_draft, counters):
+    return None
+
+
 # ------------------------------------------------------------------------------------------ weight-only FP8 decode GEMVs
 @_op("gemv_w8")
 def gemv_w8(wq: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -473,5 +517,6 @@ W4_OP_NAMES = ("gemv_w4", "gemv_swiglu_w4")
 QFM_OP_NAMES = ("gemv_fm_w4", "gemv_swiglu_fm_w4", "gemv_fm_w8", "gemv_swiglu_fm_w8")
 LM_HEAD_Q_OP_NAMES = ("lm_head_argmax_w8", "lm_head_argmax_proc_w8", "lm_head_argmax_w4", "lm_head_argmax_proc_w4")
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
+SPEC_OP_NAMES = ("attn_verify", "prompt_lookup_draft_", "spec_advance_draft_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
             "conv2d_nhwc", "attn_self", "attn_cross_kv77", "attn_consistent", "geglu", "cfg_step")
