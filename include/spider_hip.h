@@ -185,6 +185,24 @@ int spider_spec_advance_draft_i32(const int* lm_out, int* ids, int* pos, int* sl
                                   int* n_hist, int cap, const int* prompt_ids, const int* n_prompt, int pcap, const int* ngram,
                                   const int* k_draft, void* counters, int R, int B, void* stream);
 
+/* Assisted decoding (transformers generate(assistant_model = draft, num_assistant_tokens = K); csrc/spec_assist.hip): a draft engine
+ * proposes K tokens one by one, the target verifies them as the K + 1 rows of one step (spider_attn_verify_bf16 and the R-row weight
+ * route). Two launches hand tokens and cursors over between the engines; one block per sequence, nothing outside its rows is written.
+ * spider_spec_assist_push_i32: behind a draft step of Rs rows per sequence whose row rs produced draft number j (src_out its arg-max,
+ *   src_pos / src_slot its cursors, int32 [B*Rs]): row j (1 ... R - 1) of the target's t_ids / t_pos / t_slot [B*R] = (token,
+ *   src_pos + 1, src_slot + 1), and the draft engine's next single row d_ids / d_pos / d_slot / d_kv_end [B] = (token if below
+ *   draft_vocab else 0, src_pos + 1, src_slot + 1, src_slot + 2). The d_* buffers may be the source's own.
+ * spider_spec_assist_advance_i32: closes the verify step (row layout, a, hist, n_hist, kv_end, pos[0], slot[0], ids[0] and counters
+ *   as spider_spec_advance_draft_i32; rows 1 ... R - 1 are left to the next pushes) and writes the draft engine's two catch-up rows
+ *   d_ids [B*2] = (ids[a], lm_out[a]), ids at or above draft_vocab replaced by 0, d_pos / d_slot [B*2] = (pos[0] + a, + 1) /
+ *   (slot[0] + a, + 1) from the values before the advance, d_kv_end [B] = slot[0] + a + 1. */
+int spider_spec_assist_push_i32(const int* src_out, const int* src_pos, const int* src_slot, int Rs, int rs, int* t_ids, int* t_pos,
+                                int* t_slot, int R, int j, int* d_ids, int* d_pos, int* d_slot, int* d_kv_end, int draft_vocab,
+                                int B, void* stream);
+int spider_spec_assist_advance_i32(const int* lm_out, int* ids, int* pos, int* slot, int* kv_end, const int* n_draft, int* hist,
+                                   int* n_hist, int cap, void* counters, int R, int* d_ids, int* d_pos, int* d_slot, int* d_kv_end,
+                                   int draft_vocab, int B, void* stream);
+
 /* Beam search step (transformers GenerationMixin._beam_search: _get_top_k_continuations, _get_running_beams_for_next_iteration and
  * the cache reorder; num_beams / length_penalty reach it from spider.py:1471-1508 and conversation.py:151-173). rows = B * K.
  * spider_beam_partial_bf16: per row of raw bf16 logits [rows, V] and slice of 4096 tokens (nslice = ceil(V / 4096)): ws_ms

@@ -5,6 +5,7 @@
 //   spider_spec_advance_draft_i32   closes a verify step (accept, append, advance) and drafts the rows of the next one
 // Everything else of the step is the engine's existing R-row route (GEMVs, rope_kv_append with S = R, lm_head arg-max).
 #include "common.hpp"
+#include "spec_accept.hpp"
 #include <limits.h>
 
 using namespace spider;
@@ -238,11 +239,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void spec_draft_kernel(
     if (ADVANCE) {
         int nd = n_draft[b];
         nd = nd < 0 ? 0 : (nd > K ? K : nd);
-        bool ok = true;
-        for (int i = 1; i < R; ++i) {       // nd <= K <= R - 1
-            ok = ok && i <= nd && lm_out[(size_t)b * R + i - 1] == ids_b[i];
-            if (ok) a = i;
-        }
+        a = spec_accept_len(lm_out + (size_t)b * R, ids_b, nd, R);      // nd <= K <= R - 1
         last = lm_out[(size_t)b * R + a];
         if (tid <= a) s_acc[tid] = lm_out[(size_t)b * R + tid];
         if (tid == 0) {

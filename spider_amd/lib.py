@@ -69,6 +69,9 @@ SIGNATURES = {
     "spider_attn_verify_bf16": (_i, [_vp] * 8 + [_i] * 6 + [_f, _i, _vp]),
     "spider_prompt_lookup_draft_i32": (_i, [_vp, _vp, _i, _vp, _vp, _i] + [_vp] * 6 + [_i, _i, _vp]),
     "spider_spec_advance_draft_i32": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    # assisted decoding (csrc/spec_assist.hip)
+    "spider_spec_assist_push_i32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "spider_spec_assist_advance_i32": (_i, [_vp] * 8 + [_i, _vp, _i] + [_vp] * 4 + [_i, _i, _vp]),
     "spider_set_attn_inline": (_i, [_i]),
     "spider_set_attn_xlane": (_i, [_i]),
     "spider_set_gemv_sched": (_i, [_i]),

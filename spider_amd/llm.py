@@ -34,6 +34,11 @@ Prompt-lookup decoding (prompt_lookup_num_tokens=K, max_matching_ngram_size=N; o
 rows -- the last accepted token and K tokens drafted from an earlier occurrence of the sequence's last n-gram -- with the R-row
 weight streams, rope_kv_append(S = R) and a verify attention in which row r sees r more cache rows; one launch accepts the agreed
 prefix, appends it and drafts the next step (csrc/spec_decode.hip). `prompt_lookup_draft_host` / `spec_accept_host` are the definition.
+
+Assisted decoding (assistant_model=draft_engine, num_assistant_tokens=K; one greedy sequence): the drafts come from a second, smaller
+LlamaEngine instead. A round is one two-row step of the draft engine (catch-up + first draft), K - 1 single-row steps, the target's
+verify step on K + 1 rows and two kinds of small launches that carry tokens and cursors between the engines (csrc/spec_assist.hip);
+it has no host sync and is captured as one graph. `assisted_round_host` is the definition.
 """
 from __future__ import annotations
 
@@ -408,6 +413,118 @@ def spec_accept_host(ids: Sequence[int], n_draft: int, lm_out: Sequence[int]) ->
     return a
 
 
+def resolve_assisted(assistant_model, num_assistant_tokens=None, num_assistant_tokens_schedule=None,
+                     assistant_confidence_threshold=None, target=None, B: int = 1, S: int = 0, max_new_tokens: int = 0,
+                     decode_rows: int = 8, do_sample: bool = False, num_beams=1, processed: bool = False, no_repeat_ngram_size=None,
+                     output_hidden_states: bool = False, return_logits: bool = False, prompt_lookup_num_tokens=None,
+                     embeds_only: bool = False, whole_generate: bool = True):
+    """Validate `generate(assistant_model=draft, num_assistant_tokens=K)` (transformers' assisted decoding) against what the round
+    implements and return K, or None when assistant_model is None (everything stays as without it; the three companion keywords
+    then have to be None too -- they would mean nothing). `target` and `assistant_model` are read as engines: cfg.head_dim,
+    cfg.vocab, max_batch, max_len, device. K defaults to 5 and is an int in 1 .. min(decode_rows, ops.SPEC_MAX_ROWS) - 1 (the
+    drafts are rows of the target's decode graph); num_assistant_tokens_schedule may be None / "constant" and
+    assistant_confidence_threshold None / 0 (K is fixed; no heuristic and no early stop of the draft loop). The served ground is one
+    greedy sequence given as input_ids through `generate` (batch 1, num_beams 1, do_sample False), without logits processors,
+    no_repeat_ngram_size, output_hidden_states, return_logits or prompt_lookup_num_tokens, both engines at head_dim 128 on one
+    device, the draft engine distinct from the target, with max_batch >= 2 (its catch-up step has two rows) and a vocabulary no
+    larger than the target's, and S + max_new_tokens + K <= max_len of both engines (a rejected draft still writes its K / V row).
+    Everything else raises and names the argument; nothing is ignored."""
+    K = num_assistant_tokens
+    if assistant_model is None:
+        for name, v in (("num_assistant_tokens", K), ("num_assistant_tokens_schedule", num_assistant_tokens_schedule),
+                        ("assistant_confidence_threshold", assistant_confidence_threshold)):
+            if v is not None:
+                raise ValueError(f"`{name}` was given without `assistant_model`: it configures assisted decoding and means nothing alone")
+        return None
+    rows = min(decode_rows, ops.SPEC_MAX_ROWS)
+    K = 5 if K is None else K
+    if isinstance(K, bool) or not isinstance(K, int) or not (1 <= K <= rows - 1):
+        raise ValueError(f"`num_assistant_tokens` has to be an integer in [1, {rows - 1}] (the drafts are rows of the decode "
+                         f"graph's {rows}) or None, but is {K}")
+    if num_assistant_tokens_schedule not in (None, "constant"):
+        raise NotImplementedError(f"num_assistant_tokens_schedule={num_assistant_tokens_schedule!r} is not implemented: the number of "
+                                  f"drafts is fixed, pass None or 'constant'")
+    th = assistant_confidence_threshold
+    if th is not None and (isinstance(th, bool) or not isinstance(th, (int, float)) or th != 0):
+        raise NotImplementedError(f"assistant_confidence_threshold={th!r} is not implemented: every round drafts num_assistant_tokens "
+                                  f"tokens, pass None or 0")
+    if assistant_model is target:
+        raise ValueError("`assistant_model` is the engine itself: a draft engine of its own (weights, KV cache, decode states) is needed")
+    for attr in ("cfg", "max_batch", "max_len", "device", "_prefill", "_decode_step"):
+        if not hasattr(assistant_model, attr):
+            raise TypeError(f"`assistant_model` has to be a LlamaEngine, but is {type(assistant_model).__name__}")
+    if not whole_generate:
+        raise NotImplementedError("assistant_model runs through LlamaEngine.generate only: the split prefill_begin / adopt / decode_finish "
+                                  "path has no draft engine's cache to carry along")
+    if embeds_only:
+        raise NotImplementedError("assistant_model with inputs_embeds and no input_ids is not implemented: the draft engine cannot embed them")
+    if not prompt_lookup_off(prompt_lookup_num_tokens):
+        raise NotImplementedError("assistant_model together with prompt_lookup_num_tokens is not implemented: one source of drafts per call")
+    if B != 1:
+        raise NotImplementedError(f"assistant_model serves one sequence per call (transformers' assisted decoding is batch 1 too), "
+                                  f"but the batch has {B} rows")
+    if do_sample:
+        raise NotImplementedError("assistant_model with do_sample=True is not implemented (speculative sampling needs the rejection rule)")
+    if num_beams != 1:
+        raise NotImplementedError("assistant_model with num_beams > 1 is not implemented")
+    if no_repeat_ngram_size:
+        raise NotImplementedError("assistant_model with no_repeat_ngram_size is not implemented: pass None or 0")
+    if processed:
+        raise NotImplementedError("assistant_model with repetition_penalty / min_length / min_new_tokens / suppress_tokens / "
+                                  "bad_words_ids is not implemented: pass their neutral values")
+    if output_hidden_states:
+        raise NotImplementedError("assistant_model with output_hidden_states is not implemented")
+    if return_logits:
+        raise NotImplementedError("assistant_model with return_logits is not implemented")
+    d = assistant_model
+    for who, eng in (("the engine's", target), ("the assistant_model's", d)):
+        if eng.cfg.head_dim != 128:
+            raise NotImplementedError(f"assistant_model needs head_dim 128 on both engines (the verify attention), but {who} head_dim "
+                                      f"is {eng.cfg.head_dim}")
+    if d.max_batch < 2:
+        raise NotImplementedError(f"assistant_model needs a draft engine with max_batch >= 2 (its catch-up step carries two rows), "
+                                  f"but its max_batch is {d.max_batch}")
+    if torch.device(d.device) != torch.device(target.device):
+        raise NotImplementedError(f"assistant_model lives on another device ({d.device}) than the engine ({target.device})")
+    if d.cfg.vocab > target.cfg.vocab:
+        raise ValueError(f"assistant_model has a larger vocabulary ({d.cfg.vocab}) than the engine ({target.cfg.vocab}): its drafts "
+                         f"could name ids the engine does not have")
+    for who, eng in (("the engine's", target), ("the assistant_model's", d)):
+        if S + max_new_tokens + K > eng.max_len:
+            raise ValueError(f"num_assistant_tokens={K}: prompt {S} + max_new_tokens {max_new_tokens} + {K} draft rows exceed {who} "
+                             f"max_len={eng.max_len} (a rejected draft still writes its K / V row)")
+    return K
+
+
+def assisted_round_host(ids0: int, pos0: int, slot0: int, drafts: Sequence[int], lm_out: Sequence[int], draft_vocab: int,
+                        n_draft: Optional[int] = None) -> dict:
+    """One round of assisted decoding behind the draft steps and the verify step, on the host: what the launches of
+    csrc/spec_assist.hip leave in the two engines' cursors. The sequence ends with the token ids0 at position pos0 and cache slot
+    slot0 (they differ by kv_beg for a left-padded prompt); drafts = d_1 .. d_K as the draft engine proposed them one by one;
+    lm_out[r] = the target's greedy token behind row r of the verify step [ids0, d_1 .. d_K]; n_draft (default K) of the rows count
+    as drafts. Returns
+      rows      [(id, pos, slot)] of the K + 1 verify rows as the pushes left them (row 0 is the caller's)
+      feed      [(id, pos, slot, kv_end)] of the draft engine's single row behind every push: ids >= draft_vocab read as 0 THERE only
+      a         drafts accepted (`spec_accept_host`);  append = lm_out[: a + 1], the tokens that join the sequence
+      row0      (id, pos, slot) of the next round's row 0: (lm_out[a], pos0 + a + 1, slot0 + a + 1);  the target's kv_end and n_hist
+                grow by a + 1, the counters by (1, n_draft, a)
+      catch_up  dict(ids, pos, slot: two each, kv_end) of the draft engine's next two-row step: the sequence's last two tokens
+                (row a of this round and lm_out[a]; ids >= draft_vocab as 0) at (pos0 + a, pos0 + a + 1) / (slot0 + a, slot0 + a + 1),
+                kv_end = slot0 + a + 1 -- row 0 rewrites a K / V row the draft engine may hold already, which makes the round's shape
+                independent of a: after a fully accepted round the draft engine never consumed d_K, and this row supplies it."""
+    K = len(drafts)
+    nd = K if n_draft is None else max(0, min(int(n_draft), K))
+    dv = lambda t: int(t) if 0 <= int(t) < draft_vocab else 0
+    rows = [(int(ids0), int(pos0), int(slot0))] + [(int(d), pos0 + j, slot0 + j) for j, d in enumerate(drafts, 1)]
+    feed = [(dv(d), pos0 + j, slot0 + j, slot0 + j + 1) for j, d in enumerate(drafts, 1)]
+    a = spec_accept_host([r[0] for r in rows], nd, lm_out)
+    prev, last = rows[a][0], int(lm_out[a])
+    return dict(rows=rows, feed=feed, a=a, n_draft=nd, append=[int(t) for t in lm_out[:a + 1]],
+                row0=(last, pos0 + a + 1, slot0 + a + 1),
+                catch_up=dict(ids=[dv(prev), dv(last)], pos=[pos0 + a, pos0 + a + 1], slot=[slot0 + a, slot0 + a + 1],
+                              kv_end=slot0 + a + 1))
+
+
 SAMPLE_MAX_K = 64       # top_k limit of the sampling kernels (csrc/sample.hip)
 
 
@@ -677,12 +794,13 @@ class _PrefillHandle:
 
 
 class GenerateOutput:
-    def __init__(self, sequences, hidden_states=None, sequences_scores=None, beam_indices=None, prompt_lookup=None):
+    def __init__(self, sequences, hidden_states=None, sequences_scores=None, beam_indices=None, prompt_lookup=None, assisted=None):
         self.sequences = sequences
         self.hidden_states = hidden_states
         self.sequences_scores = sequences_scores     # beam search only (num_beams > 1)
         self.beam_indices = beam_indices
         self.prompt_lookup = prompt_lookup           # prompt_lookup_num_tokens only: dict(steps=, drafted=, accepted=)
+        self.assisted = assisted                     # assistant_model only: dict(steps=, drafted=, accepted=), steps = rounds
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -929,6 +1047,7 @@ class LlamaEngine:
         self._graphs = {}
         self._beam_kv_tmp = {}      # cache set -> second K / V buffer of the beam-search reorder (allocated by the first beam request)
         self.last_prompt_lookup = None      # dict(steps=, drafted=, accepted=) of the last decode_finish when it was a prompt-lookup request, else None
+        self.last_assisted = None           # the same record of the last decode_finish when it was an assistant_model request, else None
 
     def _kv(self, cache_set: int):
         while len(self._kv_sets) <= cache_set:
@@ -991,13 +1110,16 @@ class LlamaEngine:
 
     @staticmethod
     def _state_key(B: int, output_hidden_states: bool, return_logits: bool, cache_set: int, processed: bool = False,
-                   beam: Optional[tuple] = None, sample: bool = False, ngram: bool = False, lookup: int = 0) -> tuple:
+                   beam: Optional[tuple] = None, sample: bool = False, ngram: bool = False, lookup: int = 0, assist: int = 0) -> tuple:
         """key of a decode state + captured graph; requests with logits processors have their own (one more element), and so have
         beam-search requests (B = batch rows; beam = (num_beams, continuations kept per step): three more elements), sampling
         requests ("sample", behind the processors' element), requests with no_repeat_ngram_size ("ngram" as the last element;
-        they are processed requests) and prompt-lookup requests (lookup = K > 0 drafts: "lookup" and the K + 1 rows of the step;
-        one graph serves every max_matching_ngram_size)"""
+        they are processed requests), prompt-lookup requests (lookup = K > 0 drafts: "lookup" and the K + 1 rows of the step;
+        one graph serves every max_matching_ngram_size) and assistant_model requests (assist = K > 0 drafts: "assist" and the K + 1
+        rows of the verify step; the state remembers its draft engine)"""
         key = (int(B), bool(output_hidden_states), bool(return_logits), int(cache_set))
+        if assist:
+            return key + ("assist", int(assist) + 1)
         if lookup:
             return key + ("lookup", int(lookup) + 1)
         if beam is not None:
@@ -1008,16 +1130,19 @@ class LlamaEngine:
 
     def would_capture(self, B: int, output_hidden_states: bool = False, return_logits: bool = False, cache_set: int = 0,
                       processed: bool = False, num_beams: int = 1, n_eos: int = 0, do_sample: bool = False,
-                      no_repeat_ngram: bool = False, prompt_lookup_num_tokens: Optional[int] = None) -> bool:
+                      no_repeat_ngram: bool = False, prompt_lookup_num_tokens: Optional[int] = None,
+                      num_assistant_tokens: Optional[int] = None) -> bool:
         """True when the decode loop of such a request would capture its hipGraph (state missing or not captured yet).
         processed: a request with non-neutral logits processors (repetition_penalty != 1, a ban set, or EOS banned at first)
         num_beams > 1: a beam-search request of B batch rows with n_eos EOS ids (they size the continuations kept per step)
         do_sample: a sampling request (one graph serves every temperature / top_k / top_p / seed)
         no_repeat_ngram: a request with no_repeat_ngram_size > 0 (one graph serves every size)
-        prompt_lookup_num_tokens: a prompt-lookup request of that many drafts (one graph per K serves every max_matching_ngram_size)"""
+        prompt_lookup_num_tokens: a prompt-lookup request of that many drafts (one graph per K serves every max_matching_ngram_size)
+        num_assistant_tokens: an assistant_model request of that many drafts (one graph per K holds the whole round of both engines;
+        a call with another draft engine captures again)"""
         beam = (num_beams, max(2, 1 + n_eos) * num_beams) if num_beams > 1 else None
         ent = self._graphs.get(self._state_key(B, output_hidden_states, return_logits, cache_set, processed, beam, bool(do_sample),
-                                               bool(no_repeat_ngram), int(prompt_lookup_num_tokens or 0)))
+                                               bool(no_repeat_ngram), int(prompt_lookup_num_tokens or 0), int(num_assistant_tokens or 0)))
         return ent is None or ent[1] is None
 
     def _vocab_changed(self):
@@ -1077,6 +1202,10 @@ class LlamaEngine:
         q8fm = self.batched_weight_stream and self.weight_dtype == "fp8" and not w8 and B <= min(self.FP8_FM_MAX_ROWS, ops.QFM_MAX_ROWS)
         q4fm = self.batched_weight_stream and self.weight_dtype == "mxfp4" and not w4 and B <= min(self.MXFP4_FM_MAX_ROWS, ops.QFM_MAX_ROWS)
         lookup = st.get("lookup")       # prompt-lookup verify step: the layer loop below at B = R rows, attention under the causal rule
+        # a step of an assisted round (`_assist_round`: the target's verify step, the draft engine's two-row and single-row steps): it
+        # ends behind the lm_head, the round's own launches move the cursors; more than one row are rows of ONE sequence, as above
+        assist = st.get("assist")
+        one_seq = lookup is not None or (assist is not None and B > 1)
         for l, lw in enumerate(self.layers):
             if q8fm:
                 ops.gemv_fm_w8(lw["w_qkv_q8fm"], lw["w_qkv_s8"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), lw["w_qkv"].shape[0],
@@ -1098,7 +1227,7 @@ class LlamaEngine:
                 ops.gemv_fm(lw["w_qkv_fm"], h, lw["w_qkv"].shape[0], bias=lw["b_qkv"], out=st["qkv"], norm_eps=c.eps)
             else:
                 ops.gemv(lw["w_qkv"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), bias=lw["b_qkv"], out=st["qkv"])
-            if lookup is not None:  # the B rows are ONE sequence's token and its drafts: R appended K / V rows, row r sees r more of them
+            if one_seq:     # the B rows are ONE sequence's token and its drafts: R appended K / V rows, row r sees r more of them
                 ops.rope_kv_append(st["qkv"], st["pos"], st["slot"], self.cos_sin, st["q"], k_cache[l], v_cache[l],
                                    1, B, c.n_q, c.n_kv, c.head_dim)
                 ops.attn_verify(st["q"], k_cache[l], v_cache[l], st["kv_end"], B, kv_beg=st["kv_beg"], nsplit=st["nsplit"],
@@ -1146,6 +1275,9 @@ class LlamaEngine:
                 h = ops.gemv(lw["w_down"], st["act"], res=h1, out=st["h2"][l & 1])
             if hs is not None:
                 hs[l + 1].copy_(h)
+        if assist is not None:      # the model's token behind every row; pushes / advance follow in `_assist_round`
+            self._lm_head_step(st, h, st["next_ids"], None, None, fm)
+            return
         if lookup is not None:      # the model's token behind every row, then accept / append / advance / draft in one launch
             self._lm_head_step(st, h, st["next_ids"], None, None, fm)
             ops.spec_advance_draft(lookup, st["hist"], st["n_hist"])
@@ -1304,7 +1436,9 @@ class LlamaEngine:
                       min_new_tokens=0, suppress_tokens=None, bad_words_ids=None, length_penalty=1.0, early_stopping=False,
                       num_return_sequences=1, num_beam_groups=1, constraints=None, force_words_ids=None, temperature=1.0,
                       top_k=None, top_p=1.0, seed=None, no_repeat_ngram_size=None, prompt_lookup_num_tokens=None,
-                      max_matching_ngram_size=None, _whole_generate=False, _row0=0, **unused):
+                      max_matching_ngram_size=None, assistant_model=None, num_assistant_tokens=None,
+                      num_assistant_tokens_schedule=None, assistant_confidence_threshold=None, _whole_generate=False, _row0=0,
+                      **unused):
         """First half of `generate`: the prompt pass (KV cache of `cache_set` filled, first token chosen, decode cursors set), all
         ENQUEUED on the current stream without a host sync; returns a handle for `decode_finish`. Two requests can be in flight on
         two streams when they use different cache sets (prefill of one beside the decode loop of the other: SpiderFreeInfer's
@@ -1352,7 +1486,18 @@ class LlamaEngine:
         inputs_embeds) as K + 1 rows of the weight streams, verifies them in one pass (csrc/spec_decode.hip) and keeps the prefix the
         model agrees with plus the model's own next token (`spec_accept_host`): 1 .. K + 1 tokens per step, and the sequence is the
         greedy one. A state and graph of its own per K. The counters dict(steps=, drafted=, accepted=) of the call are
-        `GenerateOutput.prompt_lookup` and `last_prompt_lookup`; with sync_every > 1 they include the steps that ran past the stop."""
+        `GenerateOutput.prompt_lookup` and `last_prompt_lookup`; with sync_every > 1 they include the steps that ran past the stop.
+        assistant_model=draft_engine (a second LlamaEngine of the same tokenizer family; None = off) with num_assistant_tokens=K (an
+        int 1..7, default 5): transformers' assisted decoding for one greedy sequence through `generate` (`resolve_assisted` is the
+        served ground; num_assistant_tokens_schedule takes None / "constant", assistant_confidence_threshold None / 0). The draft
+        engine prefills the same input_ids and attention_mask into its own cache set 0; every round it proposes K tokens -- one
+        two-row step on the sequence's last two tokens, which also catches its cache up whatever the last round accepted, then K - 1
+        single-row steps -- the engine verifies them as K + 1 rows exactly as for prompt lookup, and one launch accepts, appends,
+        advances and hands the draft engine its next two rows (csrc/spec_assist.hip, `assisted_round_host`). The whole round is one
+        captured graph, keyed by K and bound to its draft engine. The sequence is the engine's greedy one whatever the draft engine
+        proposes. Its vocabulary may be smaller than the engine's: an id it does not have is fed to it as id 0, to it alone. The
+        counters dict(steps=, drafted=, accepted=) of the call (steps = rounds) are `GenerateOutput.assisted` and `last_assisted`;
+        with sync_every > 1 they include the rounds that ran past the stop. `GenerateOutput.prompt_lookup` stays None."""
         sampling = resolve_sampling(do_sample, temperature, top_k, top_p, num_return_sequences) if num_beams == 1 else None
         ngram = resolve_no_repeat_ngram(no_repeat_ngram_size)
         if sampling is not None:
@@ -1375,6 +1520,17 @@ class LlamaEngine:
             lookup = resolve_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size, B_all, S_in, max_new_tokens, self.max_len,
                                            self.DECODE_ROWS, c.head_dim, bool(do_sample), num_beams,
                                            pen != 1.0 or min_new > 0 or bool(ban), ngram, output_hidden_states, return_logits)
+        assist = None       # K of an assistant_model request
+        if (assistant_model is not None or num_assistant_tokens is not None or num_assistant_tokens_schedule is not None
+                or assistant_confidence_threshold is not None):
+            if assistant_model is not None and position_ids is not None:
+                raise NotImplementedError("assistant_model with position_ids is not implemented: the draft engine has no multimodal prompt")
+            pen, min_new, ban = resolve_logits_processors(S_in, _id_list(eos_token_id), repetition_penalty, min_length, min_new_tokens,
+                                                          suppress_tokens, bad_words_ids)
+            assist = resolve_assisted(assistant_model, num_assistant_tokens, num_assistant_tokens_schedule, assistant_confidence_threshold,
+                                      self, B_all, S_in, max_new_tokens, self.DECODE_ROWS, bool(do_sample), num_beams,
+                                      pen != 1.0 or min_new > 0 or bool(ban), ngram, output_hidden_states, return_logits,
+                                      prompt_lookup_num_tokens, embeds_only, _whole_generate)
         beam = None
         if num_beams != 1 and not _whole_generate:
             raise NotImplementedError("num_beams > 1 runs through LlamaEngine.generate only: the split prefill_begin / adopt / decode_finish "
@@ -1440,6 +1596,15 @@ class LlamaEngine:
 
         if lookup is not None:
             return self._lookup_begin(lookup, h.view(B, S, -1)[:, -1].contiguous(), next_pos, kv_beg, S, embeds_only, input_ids,
+                                      max_new_tokens, stopping_criteria, eos_token_id, pad_token_id, return_dict_in_generate,
+                                      use_graph, sync_every, cache_set)
+
+        if assist is not None:
+            # the draft engine's prompt pass: the same slots, positions and padding, ids it does not have as id 0
+            d = assistant_model
+            d_ids = torch.where(input_ids < d.cfg.vocab, input_ids, torch.zeros_like(input_ids))
+            d._prefill(d.embed_tokens(d_ids).view(B * S, -1), pos2d.view(-1), slot2d.view(-1), kv_beg if has_pad else None, B, S, None)
+            return self._assist_begin(assist, d, d_ids, h.view(B, S, -1)[:, -1].contiguous(), next_pos, kv_beg, S, input_ids,
                                       max_new_tokens, stopping_criteria, eos_token_id, pad_token_id, return_dict_in_generate,
                                       use_graph, sync_every, cache_set)
 
@@ -1548,6 +1713,82 @@ class LlamaEngine:
                               sync_every=sync_every, return_logits=False, hidden_steps=None, logits_steps=None,
                               tokens=st["hist"][:, :max_new_tokens], lookup=lookup)
 
+    def _make_assist_state(self, K: int, draft: "LlamaEngine", cache_set: int = 0) -> dict:
+        """decode state of an assistant_model request: the activations and step cursors of the K + 1 verify rows and the cache
+        cursors and token history of ONE sequence (as `_make_lookup_state`), and under "assist" the draft engine with its two
+        decode states -- `d2`, the two-row catch-up step, and `d1`, the single-row step -- and the buffers of the hand-off launches"""
+        st = self._make_state(K + 1, False, False, cache_set)
+        dv = self.device
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dv)
+        st.update(kv_end=i32(1), kv_beg=i32(1), hist=i32(1, self.max_len), n_hist=i32(1), first=i32(1))
+        d2, d1 = draft._make_state(2, False, False, 0), draft._make_state(1, False, False, 0)
+        d2.update(kv_end=i32(1), kv_beg=i32(1), assist=True)
+        d1.update(assist=True)
+        st["assist"] = dict(K=K, draft=draft, draft_graphs=draft._graphs, d2=d2, d1=d1, n_draft=i32(1),
+                            counters=torch.zeros(1, 3, dtype=torch.int64, device=dv),
+                            sp=None, tgt=dict(ids=st["cur_ids"], pos=st["pos"], slot=st["slot"]),
+                            src2=dict(out=d2["next_ids"], pos=d2["pos"], slot=d2["slot"]),
+                            src1=dict(out=d1["next_ids"], pos=d1["pos"], slot=d1["slot"]),
+                            dst=dict(ids=d1["cur_ids"], pos=d1["pos"], slot=d1["slot"], kv_end=d1["kv_end"]),
+                            catch_up=dict(ids=d2["cur_ids"], pos=d2["pos"], slot=d2["slot"], kv_end=d2["kv_end"]))
+        a = st["assist"]
+        a["sp"] = dict(lm_out=st["next_ids"], ids=st["cur_ids"], pos=st["pos"], slot=st["slot"], kv_end=st["kv_end"],
+                       n_draft=a["n_draft"], counters=a["counters"])
+        return st
+
+    def _assist_round(self, st: dict):
+        """One round of assisted decoding (graph-capturable, no host sync): the draft engine's two-row step on the sequence's last
+        two tokens, whose second arg-max is draft 1, K - 1 single-row steps for the other drafts -- every draft pushed into its row
+        of the verify step and into the draft engine's next row --, the verify step on K + 1 rows, and the closing launch."""
+        a = st["assist"]
+        d, K, vd = a["draft"], a["K"], a["draft"].cfg.vocab
+        d._decode_step(a["d2"])
+        ops.spec_assist_push(a["src2"], 1, a["tgt"], 1, a["dst"], vd)
+        for j in range(2, K + 1):
+            d._decode_step(a["d1"])
+            ops.spec_assist_push(a["src1"], 0, a["tgt"], j, a["dst"], vd)
+        self._decode_step(st)
+        ops.spec_assist_advance(a["sp"], st["hist"], st["n_hist"], a["catch_up"], vd)
+
+    def _assist_begin(self, K, draft, d_ids, last, next_pos, kv_beg, S, input_ids, max_new_tokens, stopping_criteria, eos_token_id,
+                      pad_token_id, return_dict_in_generate, use_graph, sync_every, cache_set) -> "_PrefillHandle":
+        """Behind the two prompt passes of an assistant_model request (one sequence; `last` [1, H] is the engine's final residual at
+        the last position, d_ids the prompt as the draft engine read it): the first token, the cursors of row 0, and the draft
+        engine's first catch-up rows [input_ids[-1], first token] -- all enqueued, no host sync."""
+        c = self.cfg
+        skey = self._state_key(1, False, False, cache_set, assist=K)
+        ent = self._graphs.get(skey)
+        if ent is None or ent[0]["assist"]["draft"] is not draft or ent[0]["assist"]["draft_graphs"] is not draft._graphs:
+            # (another draft engine, or one whose head moved -- `_vocab_changed` starts a new `_graphs`: the captured round holds the
+            # old launches)
+            self._graphs[skey] = ent = [self._make_assist_state(K, draft, cache_set), None]
+        st = ent[0]
+        a = st["assist"]
+        d2 = a["d2"]
+        st["kv_beg"].copy_(kv_beg)
+        d2["kv_beg"].copy_(kv_beg)
+        a["d1"]["kv_beg"].copy_(kv_beg)
+        ops.lm_head_argmax(self.lm_head, last, norm_w=self.norm, eps=c.eps, out_ids=st["first"], ws=st["lm_ws"])
+        st["cur_ids"][:1].copy_(st["first"])
+        st["pos"][:1].copy_(next_pos)
+        st["slot"][:1].fill_(S)
+        st["kv_end"].fill_(S + 1)
+        st["hist"][:, :1].copy_(st["first"].view(1, 1))
+        st["n_hist"].fill_(1)
+        a["n_draft"].fill_(K)
+        a["counters"].zero_()
+        d2["cur_ids"][:1].copy_(d_ids[0, -1:])
+        d2["cur_ids"][1:].copy_(torch.where(st["first"] < draft.cfg.vocab, st["first"], torch.zeros_like(st["first"])))
+        d2["pos"][:1].copy_(next_pos - 1)
+        d2["pos"][1:].copy_(next_pos)
+        d2["slot"].copy_(torch.tensor([S - 1, S], dtype=torch.int32))
+        d2["kv_end"].fill_(S)
+        return _PrefillHandle(B=1, S=S, st=st, skey=skey, embeds_only=False, input_ids=input_ids, max_new_tokens=max_new_tokens,
+                              stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                              output_hidden_states=False, return_dict_in_generate=return_dict_in_generate, use_graph=use_graph,
+                              sync_every=sync_every, return_logits=False, hidden_steps=None, logits_steps=None,
+                              tokens=st["hist"][:, :max_new_tokens], assist=K)
+
     @torch.no_grad()
     def adopt(self, hd: "_PrefillHandle", cache_set: int = 0) -> "_PrefillHandle":
         """Move a prefilled request into KV cache set `cache_set` (device copies of the prompt's K / V rows and of the decode cursors,
@@ -1611,6 +1852,8 @@ class LlamaEngine:
         need_check = bool(eos) or bool(stopping_criteria)
         final = None      # (padded tokens [B, k] on the host, k) once a stop condition has been met
         lookup = getattr(hd, "lookup", None)    # (K, N) of a prompt-lookup request
+        assist = getattr(hd, "assist", None)    # K of an assistant_model request: a "step" is a whole round of both engines
+        step = (lambda: self._assist_round(st)) if assist is not None else (lambda: self._decode_step(st))
 
         def check(n_done: int, already: int):
             if not need_check:
@@ -1626,36 +1869,43 @@ class LlamaEngine:
         if use_graph and graph is None and final is None and max_new_tokens > 2:
             # warm the kernels outside capture, then capture one decode step; cursors live on device
             snap = {k: st[k].clone() for k in ("cur_ids", "next_ids", "pos", "slot", "kv_end", "n_hist", "seen", "ban_step") if k in st}
+            snap_lk = []    # (buffer, copy) pairs outside the state's top level
             if lookup is not None:      # (the warm-up step's history entries and K / V rows lie past the cursors and are written again)
-                snap_lk = {k: st["lookup"][k].clone() for k in ("n_draft", "counters")}
+                snap_lk = [(st["lookup"][k], st["lookup"][k].clone()) for k in ("n_draft", "counters")]
+            if assist is not None:      # (likewise in both engines' caches; the round's last launch rewrites the draft's catch-up rows)
+                snap_lk = [(t, t.clone()) for t in [st["assist"]["counters"]] + [st["assist"]["d2"][k] for k in ("cur_ids", "pos", "slot", "kv_end")]]
             s = torch.cuda.Stream(device=dv)
             s.wait_stream(torch.cuda.current_stream(dv))
             with torch.cuda.stream(s):
-                self._decode_step(st)
+                step()
             torch.cuda.current_stream(dv).wait_stream(s)
             for k, v in snap.items():
                 st[k].copy_(v)
+            for t, v in snap_lk:
+                t.copy_(v)
             graph = torch.cuda.CUDAGraph()
             with capture_graph(graph):
-                self._decode_step(st)
+                step()
             for k, v in snap.items():   # capture does not execute; restore is a no-op safety net
                 st[k].copy_(v)
-            if lookup is not None:
-                for k, v in snap_lk.items():
-                    st["lookup"][k].copy_(v)
+            for t, v in snap_lk:
+                t.copy_(v)
             self._graphs[skey][1] = graph
-        while lookup is not None and n < max_new_tokens and final is None:
+        while (lookup is not None or assist is not None) and n < max_new_tokens and final is None:
             # prompt lookup: every verify step yields 1 .. K + 1 tokens, so `sync_every` steps (at most one per token still wanted) run
             # before the host reads how many there are; the stop checks then look at every new length, as on the path below.
             # The cache bounds them too: the host knows n tokens, step j of the block may start from n + j (K + 1) and writes K / V
             # rows up to slot S + n + j (K + 1) + K - 1, which has to stay below max_len (resolve_prompt_lookup admits j = 0).
-            K = lookup[0]
-            fit = (self.max_len - S - n - K) // (K + 1) + 1
+            # An assisted round is such a step: K + 1 verify rows in the engine's cache, fewer in the draft engine's (its last
+            # row is draft K - 1), so the shorter of the two caches bounds the rounds.
+            K = lookup[0] if lookup is not None else assist
+            cache_len = self.max_len if assist is None else min(self.max_len, st["assist"]["draft"].max_len)
+            fit = (cache_len - S - n - K) // (K + 1) + 1
             for _ in range(max(1, min(int(sync_every), max_new_tokens - n, fit))):
                 if graph is not None:
                     graph.replay()
                 else:
-                    self._decode_step(st)
+                    step()
             n = min(int(st["n_hist"].item()), max_new_tokens)
             final = check(n, checked)
             checked = n
@@ -1690,6 +1940,10 @@ class LlamaEngine:
         if lookup is not None:      # the device's counters of this call (steps that ran past a stop included)
             steps, drafted, accepted = (int(x) for x in st["lookup"]["counters"][0].tolist())
             out.prompt_lookup = self.last_prompt_lookup = dict(steps=steps, drafted=drafted, accepted=accepted)
+        self.last_assisted = None
+        if assist is not None:      # likewise; a step is a round
+            steps, drafted, accepted = (int(x) for x in st["assist"]["counters"][0].tolist())
+            out.assisted = self.last_assisted = dict(steps=steps, drafted=drafted, accepted=accepted)
         return out if return_dict_in_generate else seqs
 
     def _beam_decode(self, beam, last, next_pos, kv_beg, B, S, input_ids, max_new_tokens, eos, pad, length_penalty, early_stopping,

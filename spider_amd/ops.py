@@ -1050,6 +1050,56 @@ def spec_advance_draft(sp: dict, hist, n_hist):
               sp["prompt_ids"].shape[1], _p(sp["ngram"]), _p(sp["k_draft"]), _p(sp["counters"]), R, B, _stream())
 
 
+# --------------------------------------------------------------------------- assisted decoding (csrc/spec_assist.hip)
+def _assist_rows(ids, pos, slot, what: str, B: int):
+    """rows per sequence of three int32 cursor buffers [B * R]"""
+    _chk(ids, torch.int32, what + " ids"); _chk(pos, torch.int32, what + " pos"); _chk(slot, torch.int32, what + " slot")
+    rows = ids.numel()
+    R = rows // B
+    if rows != B * R or not 1 <= R <= SPEC_MAX_ROWS or pos.numel() != rows or slot.numel() != rows:
+        raise ValueError(f"assisted decoding: the {what} ids / pos / slot have to hold 1 ... {SPEC_MAX_ROWS} rows for each of the {B} "
+                         f"sequences, got {rows} / {pos.numel()} / {slot.numel()}")
+    return R
+
+
+def spec_assist_push(src: dict, src_row: int, tgt: dict, j: int, dst: dict, draft_vocab: int):
+    """Behind a draft step: the arg-max of row `src_row` of src = dict(out, pos, slot [B * Rs]) is draft number j. It becomes row j of
+    the verify step tgt = dict(ids, pos, slot [B * R]) one position and slot behind its source row, and the draft engine's next single
+    row dst = dict(ids, pos, slot, kv_end [B]) with ids at or above draft_vocab replaced by 0 (`llm.assisted_round_host` is the
+    definition). dst may hold src's own buffers."""
+    _chk(dst["kv_end"], torch.int32, "dst kv_end")
+    B = dst["kv_end"].numel()
+    Rs = _assist_rows(src["out"], src["pos"], src["slot"], "source", B)
+    R = _assist_rows(tgt["ids"], tgt["pos"], tgt["slot"], "target", B)
+    if _assist_rows(dst["ids"], dst["pos"], dst["slot"], "draft", B) != 1:
+        raise ValueError("spec_assist_push: the draft's next step has one row per sequence")
+    if not (0 <= src_row < Rs and 1 <= j < R):
+        raise ValueError(f"spec_assist_push: source row {src_row} of {Rs}, draft row {j} of {R}")
+    _lib.call("spider_spec_assist_push_i32", _p(src["out"]), _p(src["pos"]), _p(src["slot"]), Rs, int(src_row), _p(tgt["ids"]),
+              _p(tgt["pos"]), _p(tgt["slot"]), R, int(j), _p(dst["ids"]), _p(dst["pos"]), _p(dst["slot"]), _p(dst["kv_end"]),
+              int(draft_vocab), B, _stream())
+
+
+def spec_assist_advance(sp: dict, hist, n_hist, catch_up: dict, draft_vocab: int):
+    """Close the verify step of an assisted round: sp = dict(lm_out, ids, pos, slot [B * R], kv_end, n_draft [B], counters int64
+    [B, 3]) as for spec_advance_draft (accept by `llm.spec_accept_host`, append to hist, advance row 0, count), and write the draft
+    engine's next catch-up rows catch_up = dict(ids, pos, slot [B * 2], kv_end [B]) (`llm.assisted_round_host`)."""
+    for k in ("lm_out", "kv_end", "n_draft"):
+        _chk(sp[k], torch.int32, k)
+    _chk(hist, torch.int32, "hist"); _chk(n_hist, torch.int32, "n_hist"); _chk(sp["counters"], torch.int64, "counters")
+    _chk(catch_up["kv_end"], torch.int32, "catch_up kv_end")
+    B = n_hist.numel()
+    R = _assist_rows(sp["ids"], sp["pos"], sp["slot"], "target", B)
+    if R < 2 or _assist_rows(catch_up["ids"], catch_up["pos"], catch_up["slot"], "catch-up", B) != 2:
+        raise ValueError("spec_assist_advance: the verify step has 2 ... 8 rows per sequence, the draft's catch-up step two")
+    assert hist.dim() == 2 and hist.shape[0] == B and hist.shape[1] > 0
+    assert sp["lm_out"].numel() == B * R and sp["kv_end"].numel() == B and sp["n_draft"].numel() == B and sp["counters"].numel() == B * 3
+    assert catch_up["kv_end"].numel() == B
+    _lib.call("spider_spec_assist_advance_i32", _p(sp["lm_out"]), _p(sp["ids"]), _p(sp["pos"]), _p(sp["slot"]), _p(sp["kv_end"]),
+              _p(sp["n_draft"]), _p(hist), _p(n_hist), hist.shape[1], _p(sp["counters"]), R, _p(catch_up["ids"]), _p(catch_up["pos"]),
+              _p(catch_up["slot"]), _p(catch_up["kv_end"]), int(draft_vocab), B, _stream())
+
+
 # --------------------------------------------------------------------------- GEMM / conv / attention
 def gemm(A, W, bias=None, res=None, rowbias=None, rows_per_group=0, act=None, out_scale=1.0, out=None, out_f32=False,
          res32=None, want32=False):

@@ -264,6 +264,38 @@ def _(lm_out, ids, pos, slot, kv_end, n_draft, hist, n_hist, prompt_ids, n_promp
     return None
 
 
+# ------------------------------------------------------------------------------------------ assisted decoding
+@_op("spec_assist_push_", mutates=("t_ids", "t_pos", "t_slot", "d_ids", "d_pos", "d_slot", "d_kv_end"))
+def spec_assist_push_(src_out: torch.Tensor, src_pos: torch.Tensor, src_slot: torch.Tensor, src_row: int, t_ids: torch.Tensor,
+                      t_pos: torch.Tensor, t_slot: torch.Tensor, j: int, d_ids: torch.Tensor, d_pos: torch.Tensor,
+                      d_slot: torch.Tensor, d_kv_end: torch.Tensor, draft_vocab: int) -> None:
+    """behind a draft step: the arg-max of source row src_row becomes row j of the target's verify step (one position and slot
+    behind its source) and the draft engine's next single row (ids at or above draft_vocab read as 0 there)"""
+    ops.spec_assist_push(dict(out=src_out, pos=src_pos, slot=src_slot), src_row, dict(ids=t_ids, pos=t_pos, slot=t_slot), j,
+                         dict(ids=d_ids, pos=d_pos, slot=d_slot, kv_end=d_kv_end), draft_vocab)
+
+
+@spec_assist_push_.register_fake
+def _(src_out, src_pos, src_slot, src_row, t_ids, t_pos, t_slot, j, d_ids, d_pos, d_slot, d_kv_end, draft_vocab):
+    return None
+
+
+@_op("spec_assist_advance_", mutates=("ids", "pos", "slot", "kv_end", "hist", "n_hist", "counters", "d_ids", "d_pos", "d_slot", "d_kv_end"))
+def spec_assist_advance_(lm_out: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, kv_end: torch.Tensor,
+                         n_draft: torch.Tensor, hist: torch.Tensor, n_hist: torch.Tensor, counters: torch.Tensor,
+                         d_ids: torch.Tensor, d_pos: torch.Tensor, d_slot: torch.Tensor, d_kv_end: torch.Tensor,
+                         draft_vocab: int) -> None:
+    """end of an assisted round: the drafts lm_out agrees with are accepted and appended to hist, row 0 and kv_end advance,
+    counters int64 [B, 3] += (1, drafted, accepted), and the draft engine's two catch-up rows are written -- one launch"""
+    ops.spec_assist_advance(dict(lm_out=lm_out, ids=ids, pos=pos, slot=slot, kv_end=kv_end, n_draft=n_draft, counters=counters),
+                            hist, n_hist, dict(ids=d_ids, pos=d_pos, slot=d_slot, kv_end=d_kv_end), draft_vocab)
+
+
+@spec_assist_advance_.register_fake
+def _(lm_out, ids, pos, slot, kv_end, n_draft, hist, n_hist, counters, d_ids, d_pos, d_slot, d_kv_end, draft_vocab):
+    return None
+
+
 # ------------------------------------------------------------------------------------------ weight-only FP8 decode GEMVs
 @_op("gemv_w8")
 def gemv_w8(wq: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -518,5 +550,6 @@ QFM_OP_NAMES = ("gemv_fm_w4", "gemv_swiglu_fm_w4", "gemv_fm_w8", "gemv_swiglu_fm
 LM_HEAD_Q_OP_NAMES = ("lm_head_argmax_w8", "lm_head_argmax_proc_w8", "lm_head_argmax_w4", "lm_head_argmax_proc_w4")
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 SPEC_OP_NAMES = ("attn_verify", "prompt_lookup_draft_", "spec_advance_draft_")
+ASSIST_OP_NAMES = ("spec_assist_push_", "spec_assist_advance_")
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
             "conv2d_nhwc", "attn_self", "attn_cross_kv77", "attn_consistent", "geglu", "cfg_step")
