@@ -242,6 +242,17 @@ int spider_sample_select_f32(const float* ws_val, const int* ws_tok, const float
                              const void* seed, const int* row0, const int* n_hist, int* next_ids, int* cand_tok, float* cand_p,
                              int* n_keep, float* u, int rows, int V, int nslice, void* stream);
 
+/* Teacher-forced scoring of rows of bf16 logits (csrc/logprob.hip). Replaces, per row, `logits.float()` -> `log_softmax(-1)` ->
+ * `gather(labels)` of LlamaForCausalLM.forward(labels=...) / ForCausalLMLoss, and softmax / kl_div between two models' logits.
+ * logits [rows, ld] bf16 with V valid columns (ld >= V, ld % 8 == 0, the gap is never interpreted); targets int32 [rows].
+ * x = float(logits[r, :V]): lse[r] = m + log sum exp(x - m); logprob[r] = x[target] - lse (0 for a target outside [0, V), HF's
+ * ignore_index -100); argmax[r] = lowest id among the maxima; entropy[r] = -sum p log p. With logits_ref [rows, ld_ref] (same
+ * rules), y = float(logits_ref[r, :V]), p_ref = softmax(y): kl[r] = KL(p_ref || p) = sum p_ref (y - x) - lse_ref + lse and
+ * argmax_ref[r]; logits_ref, kl and argmax_ref are all given or all NULL. One pass, fp32, one block per row: a row's result
+ * does not depend on the other rows of the call; logits_ref == logits gives kl == 0.0 exactly. Logits must be finite. */
+int spider_logprob_rows_bf16(const void* logits, int ld, const int* targets, const void* logits_ref, int ld_ref, float* logprob,
+                             float* lse, int* argmax, float* entropy, float* kl, int* argmax_ref, int rows, int V, void* stream);
+
 /* apply_rotary_pos_emb (modeling_llama3.py:150-183; modeling_llama.py:116-123) on q,k of a fused QKV
  * projection + KV-cache append (modeling_llama.py:190-193). qkv [B*S,(n_q+2n_kv)*d]; cos_sin fp32
  * [max_pos, d] = [cos(d/2) | sin(d/2)]; q_out [B*S,n_q,d]; caches [B,n_kv,T_max,d]. */

@@ -57,6 +57,8 @@ SIGNATURES = {
     "spider_kv_row_gather_bf16": (_i, [_vp] * 7 + [_i] * 7 + [_vp]),
     "spider_sample_partial_bf16": (_i, [_vp] * 11 + [_i] * 3 + [_vp]),
     "spider_sample_select_f32": (_i, [_vp] * 13 + [_i] * 3 + [_vp]),
+    # teacher-forced scoring of logits rows (csrc/logprob.hip)
+    "spider_logprob_rows_bf16": (_i, [_vp, _i, _vp, _vp, _i] + [_vp] * 6 + [_i, _i, _vp]),
     "spider_gemv_fm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "spider_gemv_swiglu_fm_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "spider_lm_head_argmax_fm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),

@@ -613,6 +613,139 @@ def sample_token_host(x: torch.Tensor, temperature: float, top_k: int, top_p: fl
     return dict(tokens=idx, x=xs, p=p, cum=cum, n_keep=n_keep, S=S, rank=rank, token=int(idx[rank]))
 
 
+IGNORE_INDEX = -100     # HF's ignore_index: a label that is not scored
+
+
+class ScoreOutput:
+    """Result of `LlamaEngine.score` / `score_host`. Every per-position field is [B, S] and aligned to the LABEL it scores: index t
+    comes from the logits row t - 1 (HF's shift); index 0 and ignored positions hold 0 (argmax: -1) and `mask` is False there.
+      token_logprobs  log p(labels[b, t] | tokens before t)      mask      the scored positions
+      argmax          the model's own prediction for index t     entropy   of that predictive distribution (nats)
+      loss = -sum(token_logprobs) / n_tokens over the mask (what LlamaForCausalLM(...).loss returns; NaN when n_tokens == 0),
+      n_tokens, perplexity = exp(loss)
+    with a reference distribution (`other` / `logits_ref`): kl = KL(reference || this) per position, mean_kl over the mask and
+    top1_agree = the share of scored positions where both arg-maxima agree; with return_logits the bf16 logits [B, S, V]."""
+
+    def __init__(self, token_logprobs, mask, argmax, entropy, loss, n_tokens, kl=None, mean_kl=None, top1_agree=None, logits=None):
+        self.token_logprobs, self.mask, self.argmax, self.entropy = token_logprobs, mask, argmax, entropy
+        self.loss, self.n_tokens = float(loss), int(n_tokens)
+        self.perplexity = math.exp(min(self.loss, 709.0))       # (NaN stays NaN)
+        self.kl, self.mean_kl, self.top1_agree, self.logits = kl, mean_kl, top1_agree, logits
+
+    def __getitem__(self, k):
+        return getattr(self, k)
+
+
+def score_targets(labels: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The label each position is scored against, int64 [B, S] on the CPU: labels[b, t] where t >= 1, attention_mask[b, t] != 0 and
+    the label is not -100; IGNORE_INDEX elsewhere. This is the mask of `score` and `score_host`. A left-padded row's first real
+    token is scored from the logits of a pad position, as transformers does: give it label -100 to leave it out."""
+    tg = labels.detach().to("cpu", torch.int64).clone()
+    tg[:, 0] = IGNORE_INDEX
+    if attention_mask is not None:
+        tg[attention_mask.detach().cpu() == 0] = IGNORE_INDEX
+    return tg
+
+
+def _score_assemble(tg, lp, am, ent, kl=None, am_ref=None, logits=None) -> ScoreOutput:
+    """per-row results (row (b, s) of the logits: [B, S]) -> the label-aligned, masked fields of a ScoreOutput"""
+    mask = tg != IGNORE_INDEX
+    mask = mask.to(lp.device)
+
+    def shift(v, fill):
+        out = torch.full_like(v, fill)
+        out[:, 1:] = v[:, :-1]
+        return torch.where(mask, out, torch.full_like(out, fill))
+    tlp, amx, en = shift(lp, 0), shift(am, -1), shift(ent, 0)
+    n = int(mask.sum())
+    loss = float(-tlp.double().sum() / n) if n else float("nan")
+    o = ScoreOutput(tlp, mask, amx, en, loss, n, logits=logits)
+    if kl is not None:
+        o.kl = shift(kl, 0)
+        o.mean_kl = float(o.kl.double().sum() / n) if n else float("nan")
+        o.top1_agree = float((shift(am_ref, -1) == amx)[mask].double().mean()) if n else float("nan")
+    return o
+
+
+def score_host(logits: torch.Tensor, labels: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+               logits_ref: Optional[torch.Tensor] = None) -> ScoreOutput:
+    """Host restatement in fp64 of `LlamaEngine.score` on given logits [B, S, V] (any float dtype; the values are taken as they are):
+    the definition of every ScoreOutput field. Row t - 1 scores labels[b, t] (`score_targets` is the mask): x = logits[b, t - 1],
+    lse = log sum exp x, token_logprobs = x[label] - lse, argmax = the lowest id among the maxima, entropy = -sum p log p,
+    loss = the mean negative log-probability over the mask = F.cross_entropy(logits[:, :-1], labels[:, 1:], ignore_index=-100) of
+    LlamaForCausalLM.forward(labels=). With logits_ref (the reference distribution): kl = sum p_ref (log p_ref - log p)."""
+    x = logits.detach().double().cpu()
+    B, S, V = x.shape
+    tg = score_targets(labels, attention_mask)
+    if tuple(tg.shape) != (B, S):
+        raise ValueError(f"labels must be [{B}, {S}], got {tuple(tg.shape)}")
+    if int(tg.max()) >= V or bool(((tg < 0) & (tg != IGNORE_INDEX)).any()):
+        raise ValueError(f"labels must be in [0, {V}) or {IGNORE_INDEX}")
+    nxt = torch.full_like(tg, IGNORE_INDEX)
+    nxt[:, :-1] = tg[:, 1:]                     # the label row (b, s) is scored against
+    lsm = torch.log_softmax(x, -1)
+    lp = torch.where(nxt >= 0, lsm.gather(-1, nxt.clamp(min=0)[..., None])[..., 0], torch.zeros(B, S, dtype=torch.float64))
+    ids = torch.arange(V)
+
+    def first_max(v):
+        return torch.where(v == v.amax(-1, keepdim=True), ids, torch.full_like(ids, V)).amin(-1)
+    ent = -(lsm.exp() * lsm).sum(-1)
+    kl = am_ref = None
+    if logits_ref is not None:
+        y = logits_ref.detach().double().cpu()
+        if y.shape != x.shape:
+            raise ValueError(f"logits_ref must be {tuple(x.shape)}, got {tuple(y.shape)}")
+        lsr = torch.log_softmax(y, -1)
+        kl = (lsr.exp() * (lsr - lsm)).sum(-1)
+        am_ref = first_max(y)
+    return _score_assemble(tg, lp, first_max(x), ent, kl, am_ref)
+
+
+def resolve_score(vocab: int, hidden: int, max_batch: int, max_len: int, mrope: bool, input_ids=None, inputs_embeds=None,
+                  attention_mask=None, position_ids=None, labels=None):
+    """The served ground of `LlamaEngine.score`, checked on the host before anything is enqueued (the input rules of prefill_begin);
+    a violation raises ValueError naming the argument. Returns (B, S, targets) with targets = `score_targets` of the labels
+    (default: input_ids)."""
+    if (input_ids is None) == (inputs_embeds is None):
+        raise ValueError("score: exactly one of input_ids and inputs_embeds must be given")
+    if input_ids is not None:
+        if input_ids.dim() != 2 or input_ids.dtype not in (torch.int32, torch.int64) or input_ids.numel() == 0:
+            raise ValueError(f"input_ids must be a non-empty integer tensor [B, S], got {tuple(input_ids.shape)} {input_ids.dtype}")
+        B, S = input_ids.shape
+        ic = input_ids.detach().cpu()
+        if int(ic.min()) < 0 or int(ic.max()) >= vocab:
+            raise ValueError(f"input_ids must be in [0, {vocab})")
+        name = "input_ids"
+    else:
+        if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != hidden or inputs_embeds.numel() == 0:
+            raise ValueError(f"inputs_embeds must be [B, S, {hidden}], got {tuple(inputs_embeds.shape)}")
+        B, S = inputs_embeds.shape[:2]
+        name = "inputs_embeds"
+        if labels is None:
+            raise ValueError("labels are required with inputs_embeds alone (there are no ids to default to)")
+    if B > max_batch or S > max_len:
+        raise ValueError(f"{name}: batch {B} / length {S} exceed the preallocated KV cache ({max_batch} x {max_len})")
+    if attention_mask is not None:
+        if tuple(attention_mask.shape) != (B, S):
+            raise ValueError(f"attention_mask must be [{B}, {S}], got {tuple(attention_mask.shape)}")
+        am = (attention_mask.detach().cpu() != 0).to(torch.int64)
+        if bool((am[:, 1:] < am[:, :-1]).any()) or bool((am[:, -1] == 0).any()):
+            raise ValueError("attention_mask must describe LEFT padding: zeros, then ones up to the last position of every row")
+    if position_ids is not None:
+        if not mrope:
+            raise ValueError("position_ids with 3 components need a model with mrope_section (Qwen2.5-Omni thinker)")
+        if tuple(position_ids.shape) != (3, B, S):
+            raise ValueError(f"position_ids must be [3, {B}, {S}], got {tuple(position_ids.shape)}")
+    if labels is None:
+        labels = input_ids
+    if tuple(labels.shape) != (B, S) or labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"labels must be an integer tensor [{B}, {S}], got {tuple(labels.shape)} {labels.dtype}")
+    tg = score_targets(labels, attention_mask)
+    if int(tg.max()) >= vocab or bool(((tg < 0) & (tg != IGNORE_INDEX)).any()):
+        raise ValueError(f"labels must be in [0, {vocab}) or {IGNORE_INDEX} (ignored)")
+    return B, S, tg
+
+
 def finalize_greedy(tokens: torch.Tensor, eos: Optional[List[int]], pad: Optional[int], stopping_criteria,
                     prompt: Optional[torch.Tensor], checked: int = 0):
     """HF greedy-search bookkeeping (`_sample` with do_sample=False, as driven by spider.py:1492-1508), applied to a
@@ -1679,6 +1812,106 @@ class LlamaEngine:
                               output_hidden_states=output_hidden_states, return_dict_in_generate=return_dict_in_generate,
                               use_graph=use_graph, sync_every=sync_every, return_logits=return_logits, hidden_steps=hidden_steps,
                               logits_steps=logits_steps, tokens=tokens)
+
+    # ------------------------------------------------------------------ teacher-forced scoring
+    SCORE_SCRATCH_BYTES = 320 << 20     # bf16 logits scratch of one chunk (1024 rows at V = 152064)
+    SCORE_CHUNK_ROWS = None             # rows per chunk; None = sized from the scratch and the GEMM's 2 GiB output limit
+
+    def _score_head(self):
+        """the lm_head as `score` multiplies it: [ld, H] with ld = V rounded up to 8, so that the logits rows are 16-byte groups and
+        the GEMM runs its usual N % 8 == 0 forms whatever the vocabulary. A vocabulary that is a multiple of 8 uses `lm_head`
+        itself; any other gets a copy with zero rows appended (their logits are 0 and never read), rebuilt when the head changes."""
+        W = self.lm_head
+        V, H = W.shape
+        ld = (V + 7) // 8 * 8
+        if ld == V:
+            return W, ld
+        tag = (W.data_ptr(), W._version, V)
+        cached = getattr(self, "_score_head_pad", None)
+        if cached is None or cached[0] != tag:
+            Wp = torch.zeros(ld, H, dtype=BF16, device=self.device)
+            Wp[:V].copy_(W)
+            self._score_head_pad = cached = (tag, Wp)
+        return cached[1], ld
+
+    def _score_logits(self, input_ids, inputs_embeds, attention_mask, position_ids, B, S, cache_set):
+        """the prompt pass of `prefill_begin` on these inputs: the final residual stream [B * S, H]"""
+        dv = self.device
+        h0 = (inputs_embeds.to(device=dv, dtype=BF16).contiguous() if input_ids is None else self.embed_tokens(input_ids.to(dv)))
+        am = (attention_mask.to(dv).to(torch.int32) if attention_mask is not None else torch.ones(B, S, dtype=torch.int32, device=dv))
+        pos2d = (am.cumsum(-1) - 1).clamp(min=0).to(torch.int32).contiguous()
+        slot2d = torch.arange(S, dtype=torch.int32, device=dv)[None].expand(B, S).contiguous()
+        kv_beg = (S - am.sum(-1)).to(torch.int32).contiguous()
+        has_pad = attention_mask is not None and bool((am == 0).any())
+        if position_ids is not None:
+            pos3 = position_ids.to(device=dv, dtype=torch.int32).contiguous()
+            return self._prefill(h0.view(B * S, -1), pos3.view(3, -1), slot2d.view(-1), kv_beg if has_pad else None, B, S, None, mrope=True,
+                                 cache_set=cache_set)
+        return self._prefill(h0.view(B * S, -1), pos2d.view(-1), slot2d.view(-1), kv_beg if has_pad else None, B, S, None,
+                             cache_set=cache_set)
+
+    @torch.no_grad()
+    def score(self, input_ids: Optional[torch.Tensor] = None, inputs_embeds: Optional[torch.Tensor] = None,
+              attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
+              labels: Optional[torch.Tensor] = None, other: Optional["LlamaEngine"] = None, cache_set: int = 0,
+              return_logits: bool = False) -> ScoreOutput:
+        """Teacher-forced pass: the `logits` / `loss` half of LlamaForCausalLM.forward(input_ids, labels=...), and the divergence
+        from a second engine. The inputs follow the rules of `prefill_begin` (left padding by attention_mask, position_ids
+        [3, B, S] with mrope_section, B <= max_batch, S <= max_len; `resolve_score` raises ValueError naming the argument).
+        labels [B, S] default to input_ids and are required with inputs_embeds alone; positions with attention_mask == 0 or label
+        -100 are ignored, labels >= vocab raise (`score_targets`).
+        The prompt pass runs as in `prefill_begin` (it fills the KV cache of `cache_set`); the rows of the final residual stream
+        then go in chunks through the final RMSNorm, the lm_head GEMM into a bf16 scratch [chunk, ld] and `ops.logprob_rows`
+        (csrc/logprob.hip): bf16 logits, then an fp32 log-softmax -- HF's arithmetic. A quantised engine (weight_dtype /
+        lm_head_dtype) is exactly a bf16 model on W_eff, which is what this pass multiplies: it measures that model exactly.
+        other: a second LlamaEngine of the same vocabulary on the same device (else ValueError) runs the same inputs through its own
+        prompt pass (its cache set 0) and is the REFERENCE distribution: kl = KL(other || self) per position, mean_kl, top1_agree.
+        return_logits=True (tests and small cases: B * S * V bf16) also returns the logits [B, S, V].
+        `score_host` is the definition of every field of the result. No decode state or captured graph is made or touched."""
+        c, dv = self.cfg, self.device
+        B, S, tg = resolve_score(c.vocab, c.hidden, self.max_batch, self.max_len, c.mrope_section is not None, input_ids, inputs_embeds,
+                                 attention_mask, position_ids, labels)
+        if other is not None:
+            if not isinstance(other, LlamaEngine) or other.cfg.vocab != c.vocab or other.device != dv:
+                raise ValueError("other must be a LlamaEngine of the same vocabulary on the same device")
+            if input_ids is None and other.cfg.hidden != c.hidden:
+                raise ValueError("other: scoring inputs_embeds against a second engine needs the same hidden size")
+            if B > other.max_batch or S > other.max_len:
+                raise ValueError(f"other: batch {B} / length {S} exceed its preallocated KV cache ({other.max_batch} x {other.max_len})")
+        if int(cache_set) < 0:
+            raise ValueError(f"cache_set={cache_set}")
+        V = c.vocab
+        R = B * S
+        nxt = torch.full_like(tg, IGNORE_INDEX)
+        nxt[:, :-1] = tg[:, 1:]                     # the label row (b, s) of the logits is scored against
+        targets = nxt.to(device=dv, dtype=torch.int32).view(-1).contiguous()
+        engines = [self] if other is None or other is self else [self, other]
+        hs = [e._score_logits(input_ids, inputs_embeds, attention_mask, position_ids, B, S, cache_set if e is self else 0) for e in engines]
+        heads = [e._score_head() for e in engines]
+        ld = heads[0][1]
+        chunk = self.SCORE_CHUNK_ROWS or max(1, min(1024, self.SCORE_SCRATCH_BYTES // (2 * ld), ((1 << 31) - 1) // (2 * ld)))
+        chunk = min(int(chunk), R)
+        scratch = [torch.empty(chunk, ld, dtype=BF16, device=dv) for _ in engines]
+        f32 = lambda: torch.empty(R, dtype=torch.float32, device=dv)
+        i32 = lambda: torch.empty(R, dtype=torch.int32, device=dv)
+        res = dict(logprob=f32(), argmax=i32(), entropy=f32())
+        if other is not None:
+            res["kl"], res["argmax_ref"] = f32(), i32()
+        full = torch.empty(R, V, dtype=BF16, device=dv) if return_logits else None
+        for a in range(0, R, chunk):
+            n = min(chunk, R - a)
+            for e, h, (W, _), sc in zip(engines, hs, heads, scratch):
+                ops.gemm(ops.rmsnorm(h[a:a + n], e.norm, e.cfg.eps), W, out=sc[:n])
+            ref = None if other is None else scratch[-1][:n]        # (other is self: the same rows are their own reference)
+            o = ops.logprob_rows(scratch[0][:n], targets[a:a + n], V, logits_ref=ref)
+            for k in res:
+                res[k][a:a + n].copy_(o[k])
+            if full is not None:
+                full[a:a + n].copy_(scratch[0][:n, :V])
+        v = lambda k: res[k].view(B, S)
+        return _score_assemble(tg, v("logprob"), v("argmax").to(torch.int64), v("entropy"), v("kl") if other is not None else None,
+                               v("argmax_ref").to(torch.int64) if other is not None else None,
+                               full.view(B, S, V) if full is not None else None)
 
     def _lookup_begin(self, lookup, last, next_pos, kv_beg, S, embeds_only, input_ids, max_new_tokens, stopping_criteria,
                       eos_token_id, pad_token_id, return_dict_in_generate, use_graph, sync_every, cache_set) -> "_PrefillHandle":

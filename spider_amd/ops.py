@@ -925,6 +925,44 @@ def sample_select(sm: dict, n_hist, next_ids, V: int):
               _p(sm["u"]), rows, V, ns, _stream())
 
 
+def _rows_ld(t, name):
+    """(rows, ld, width) of a 2-D bf16 tensor of unit column stride: a contiguous [rows, ld] tensor or a column slice of one"""
+    _chk(t, BF16, name, contiguous=False)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % 8:
+        raise ValueError(f"{name}: expected a 2-D tensor [rows, width] with unit column stride and a row stride that is a multiple of 8 "
+                         f"(pad the rows: the kernel reads whole 16-byte groups), got shape {tuple(t.shape)} strides {t.stride()}")
+    return t.shape[0], t.stride(0), t.shape[1]
+
+
+def logprob_rows(logits, targets, V: Optional[int] = None, logits_ref=None) -> dict:
+    """Teacher-forced scoring of logits rows in one pass (csrc/logprob.hip; `llm.score_host` is the definition): replaces
+    `logits.float()` -> `log_softmax` -> `gather` / ForCausalLMLoss per row. logits bf16 [rows, ld] with the first V columns valid
+    (default: all; ld = the row stride, a multiple of 8 -- a column slice `buf[:, :V]` of a padded buffer works as well); targets
+    int32 [rows], ids outside [0, V) (HF's ignore_index -100) score 0. Returns fp32 / int32 [rows] tensors: logprob, lse, argmax
+    (lowest id among the maxima), entropy; with logits_ref (same layout rules, its own stride) also kl = KL(softmax(ref) ||
+    softmax(logits)) and argmax_ref. The inputs are not written."""
+    rows, ld, width = _rows_ld(logits, "logits")
+    V = width if V is None else int(V)
+    if not 1 <= V <= width:
+        raise ValueError(f"V={V} must be in [1, {width}] (the width of logits)")
+    _chk(targets, torch.int32, "targets")
+    if targets.numel() != rows:
+        raise ValueError(f"targets: expected {rows} entries, got {targets.numel()}")
+    dv = logits.device
+    f32 = lambda: torch.empty(rows, dtype=torch.float32, device=dv)
+    i32 = lambda: torch.empty(rows, dtype=torch.int32, device=dv)
+    out = dict(logprob=f32(), lse=f32(), argmax=i32(), entropy=f32())
+    ld_ref = 0
+    if logits_ref is not None:
+        rrows, ld_ref, rwidth = _rows_ld(logits_ref, "logits_ref")
+        if rrows != rows or rwidth < V:
+            raise ValueError(f"logits_ref: expected [{rows}, >= {V}], got {tuple(logits_ref.shape)}")
+        out["kl"], out["argmax_ref"] = f32(), i32()
+    _lib.call("spider_logprob_rows_bf16", _p(logits), ld, _p(targets), _p(logits_ref), ld_ref, _p(out["logprob"]), _p(out["lse"]),
+              _p(out["argmax"]), _p(out["entropy"]), _p(out.get("kl")), _p(out.get("argmax_ref")), rows, V, _stream())
+    return out
+
+
 def rope_kv_append(qkv, pos, slot, cos_sin, q_out, k_cache, v_cache, B, S, n_q, n_kv, d, mrope_section=None):
     """pos [B*S] int32, or [3, B*S] with mrope_section=(t, h, w) rotary pairs per component (Qwen2.5-Omni: 16, 24, 24)."""
     _chk(qkv, BF16, "qkv"); _chk(pos, torch.int32, "pos"); _chk(slot, torch.int32, "slot")

@@ -738,6 +738,22 @@ class QwenOmniThinker:
         h = self.llm.prefill_begin(inputs_embeds=emb, position_ids=pos, attention_mask=attention_mask, max_new_tokens=max_new_tokens, **kw)
         return (h, input_ids)
 
+    @torch.no_grad()
+    def score(self, input_ids, attention_mask=None, labels=None, other=None, cache_set: int = 0, return_logits: bool = False,
+              **tower_inputs):
+        """Teacher-forced scoring of a multimodal prompt: `prepare_inputs` (towers, embedding splice, rotary positions), then
+        `LlamaEngine.score(inputs_embeds=, position_ids=)`. labels default to input_ids with the pad positions and the image /
+        video / audio placeholder ids set to -100 (a placeholder is not a token the model predicts). -> ScoreOutput."""
+        emb, pos = self.prepare_inputs(input_ids, attention_mask, **tower_inputs)
+        if labels is None:
+            labels = input_ids.detach().cpu().to(torch.int64).clone()
+            for tok in (self.ids.image, self.ids.video, self.ids.audio):
+                labels[labels == tok] = -100
+            if attention_mask is not None:
+                labels[attention_mask.detach().cpu() == 0] = -100
+        return self.llm.score(inputs_embeds=emb, position_ids=pos, attention_mask=attention_mask, labels=labels, other=other,
+                              cache_set=cache_set, return_logits=return_logits)
+
     def would_capture(self, input_ids, attention_mask=None, cache_set: int = 0, pixel_values=None, image_grid_thw=None,
                       pixel_values_videos=None, video_grid_thw=None, input_features=None, feature_attention_mask=None,
                       audio_feature_lengths=None, output_hidden_states: bool = False, return_logits: bool = False, decode: bool = True,

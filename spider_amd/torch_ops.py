@@ -539,6 +539,27 @@ def _(packed_u8, desc, tabs, lut, rows, patch, merge, temporal, tmp_bytes, max_h
     return packed_u8.new_empty(rows, 3 * temporal * patch * patch, dtype=torch.float32 if f32 else BF16)
 
 
+# ------------------------------------------------------------------------------------------ teacher-forced scoring of logits rows
+@_op("logprob_rows")
+def logprob_rows(logits: torch.Tensor, targets: torch.Tensor, V: int, logits_ref: Optional[torch.Tensor] = None
+                 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`logits.float()` -> `log_softmax` -> `gather(targets)` (ForCausalLMLoss) per row of bf16 logits [rows, ld] with V valid
+    columns, in one pass: (logprob, lse, argmax, entropy, kl, argmax_ref), fp32 / int32 [rows]; kl = KL(softmax(logits_ref) ||
+    softmax(logits)); without logits_ref the last two are empty. Targets outside [0, V) (ignore_index -100) score 0."""
+    o = ops.logprob_rows(logits, targets, V, logits_ref)
+    kl = o["kl"] if logits_ref is not None else logits.new_empty(0, dtype=torch.float32)
+    ar = o["argmax_ref"] if logits_ref is not None else logits.new_empty(0, dtype=torch.int32)
+    return o["logprob"], o["lse"], o["argmax"], o["entropy"], kl, ar
+
+
+@logprob_rows.register_fake
+def _(logits, targets, V, logits_ref=None):
+    rows, n = logits.shape[0], (logits.shape[0] if logits_ref is not None else 0)
+    f32 = lambda k: logits.new_empty(k, dtype=torch.float32)
+    i32 = lambda k: logits.new_empty(k, dtype=torch.int32)
+    return f32(rows), f32(rows), i32(rows), f32(rows), f32(n), i32(n)
+
+
 # the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 and MXFP4 GEMVs (row-major and fragment-major) and lm_heads, the safety-checker
 # ops and the audio and image feature ops above are listed apart
 SAFETY_OP_NAMES = ("clip_preprocess", "safety_decide", "image_blackout_")
@@ -551,5 +572,6 @@ LM_HEAD_Q_OP_NAMES = ("lm_head_argmax_w8", "lm_head_argmax_proc_w8", "lm_head_ar
 DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 SPEC_OP_NAMES = ("attn_verify", "prompt_lookup_draft_", "spec_advance_draft_")
 ASSIST_OP_NAMES = ("spec_assist_push_", "spec_assist_advance_")
+SCORE_OP_NAMES = ("logprob_rows",)
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
             "conv2d_nhwc", "attn_self", "attn_cross_kv77", "attn_consistent", "geglu", "cfg_step")
