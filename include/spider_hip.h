@@ -253,6 +253,18 @@ int spider_sample_select_f32(const float* ws_val, const int* ws_tok, const float
 int spider_logprob_rows_bf16(const void* logits, int ld, const int* targets, const void* logits_ref, int ld_ref, float* logprob,
                              float* lse, int* argmax, float* entropy, float* kl, int* argmax_ref, int rows, int V, void* stream);
 
+/* Calibrated MXFP4 (GPTQ on MX blocks; csrc/gptq.hip, `llm.quantize_mxfp4_gptq` is the definition): the quantise-and-compensate
+ * sweep over ONE group of nblocks (1..4) consecutive MX blocks, columns [j0, j0 + 32 nblocks), for all N rows, in fp32.
+ * Wt [K, N] fp32: the K-major working copy of the weights (column j of every row contiguous), read only; U [K, K] fp32 row-major:
+ * the upper Cholesky factor of H^-1, of which the group's diagonal block is read. Per row and block: the E8M0 byte from the amax
+ * of the current weights by quantize_mxfp4's rule, then per column in order the e2m1 code (ties to the even significand,
+ * saturating at code 7), e = (w - q) / U[j, j], and w' -= e U[j, j'] for the later columns j' of the group. Written: blocks
+ * [N, K / 2] uint8 (16 bytes per row and block, quantize_mxfp4's layout), scales [N, K / 32] uint8, Et [32 nblocks, N] fp32 (E
+ * transposed; rows of an Et with at least 32 nblocks rows). The caller owes the columns behind the group
+ * Wt[j0 + 32 nblocks:, :] -= U[j0 : j0 + 32 nblocks, j0 + 32 nblocks:]^T Et before the next launch. */
+int spider_gptq_mxfp4_sweep_f32(const float* Wt, const float* U, void* blocks, void* scales, float* Et, int N, int K, int j0,
+                                int nblocks, void* stream);
+
 /* apply_rotary_pos_emb (modeling_llama3.py:150-183; modeling_llama.py:116-123) on q,k of a fused QKV
  * projection + KV-cache append (modeling_llama.py:190-193). qkv [B*S,(n_q+2n_kv)*d]; cos_sin fp32
  * [max_pos, d] = [cos(d/2) | sin(d/2)]; q_out [B*S,n_q,d]; caches [B,n_kv,T_max,d]. */

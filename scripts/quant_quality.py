@@ -8,6 +8,10 @@ is perplexity, delta NLL against bf16, mean KL(bf16 || quantised) per scored tok
 --tokens: a .pt / .npy / .json file holding a [N, S] integer array (or a list of equally long id lists). Without it the ids are
 uniform random, and with random weights NOTHING here says anything about text: the synthetic run records how far the formats move
 the output distribution of a random network of the true shapes, on the device instead of on toy heads on the host.
+--calibrate FILE [--damp D]: also the "mxfp4 (gptq)" rows, without and with the calibrated head: the MXFP4 codes chosen by GPTQ on
+the token ids of FILE (same formats; `LlamaEngine(calibration=...)`). FILE "random" draws --seqs sequences of uniform random ids
+with another seed than the scored ones. The scored sequences have to be disjoint from the calibration sequences: the rows
+measure held-out tokens.
 The quantised engines are built one after the other from the bf16 engine's own tensors (a quantised engine is exactly a bf16 model
 on W_eff, which is what the scoring pass multiplies), so at most two engines are alive at once."""
 import argparse
@@ -25,6 +29,8 @@ ap.add_argument("--tokens", default=None, help="[N, S] token ids (.pt / .npy / .
 ap.add_argument("--seqs", type=int, default=4, help="random sequences when --tokens is not given")
 ap.add_argument("--len", type=int, default=512, dest="seq_len", help="their length")
 ap.add_argument("--layers", type=int, default=None, help="--shapes only: keep this many layers (a quicker synthetic run)")
+ap.add_argument("--calibrate", default=None, help='[n, S] token ids to calibrate the "mxfp4 (gptq)" rows on (a file as --tokens, or "random")')
+ap.add_argument("--damp", type=float, default=0.01, help="GPTQ damping of --calibrate")
 ap.add_argument("--out", default=None, help="also write the report to this file")
 args = ap.parse_args()
 if (args.path is None) == (args.shapes is None):
@@ -94,6 +100,17 @@ else:
 if args.path is None or args.tokens is None:
     say("Random weights and random ids say nothing about text: these figures measure how far the number formats move the output "
         "distribution of a network of the true shapes, not the quality of any model.")
+cal_tokens = None
+if args.calibrate:
+    if args.calibrate == "random":
+        cal_tokens = torch.randint(0, cfg.vocab, (args.seqs, S), generator=torch.Generator().manual_seed(1))
+        what += f"; calibration: {args.seqs} sequences of {S} uniform random ids of another seed"
+    else:
+        cal_tokens = load_tokens(args.calibrate)
+        what += f"; calibration: {cal_tokens.shape[0]} sequences of {cal_tokens.shape[1]} ids from {args.calibrate}"
+    scored = {tuple(r) for r in tokens.tolist()}
+    if any(tuple(r) in scored for r in cal_tokens.tolist()):
+        ap.error("--calibrate: a calibration sequence is also a scored sequence; the gptq rows have to be scored on held-out tokens")
 say(what)
 
 
@@ -122,6 +139,18 @@ for wd, hd in (("fp8", "bf16"), ("fp8", "fp8"), ("mxfp4", "bf16"), ("mxfp4", "mx
     say(f"  {wd} / head {hd}: NLL {nll:.5f}  mean KL {kl:.5f}  top-1 agreement {agree:.4f}")
     del eng
     torch.cuda.empty_cache()
+if cal_tokens is not None:
+    for hd in ("bf16", "mxfp4"):
+        eng = LlamaEngine(cfg, weights, dev, max_batch=1, max_len=max(S, cal_tokens.shape[1]), weight_dtype="mxfp4", lm_head_dtype=hd,
+                          calibration=dict(input_ids=cal_tokens, damp=args.damp))
+        worst = max(eng.calibration["matrices"], key=lambda m: m[3] / m[2])
+        nll, kl, agree, _ = run(eng, other=base)
+        rows.append(("mxfp4 (gptq)", hd + (" (gptq)" if hd == "mxfp4" else ""), nll, kl, agree))
+        say(f"  mxfp4 (gptq) / head {hd}: NLL {nll:.5f}  mean KL {kl:.5f}  top-1 agreement {agree:.4f}   [{eng.calibration['n_tokens']} calibration "
+            f"tokens; proxy loss gptq / rtn between {min(m[3] / m[2] for m in eng.calibration['matrices']):.3f} and {worst[3] / worst[2]:.3f} "
+            f"(layer {worst[0]} {worst[1]})]")
+        del eng
+        torch.cuda.empty_cache()
 say("")
 say(f"{n} scored tokens; KL(bf16 || engine) and top-1 agreement are against the bf16 engine on the same positions")
 say("| weight_dtype | lm_head_dtype | perplexity | NLL | delta NLL vs bf16 | mean KL | top-1 agreement |")

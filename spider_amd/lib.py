@@ -59,6 +59,8 @@ SIGNATURES = {
     "spider_sample_select_f32": (_i, [_vp] * 13 + [_i] * 3 + [_vp]),
     # teacher-forced scoring of logits rows (csrc/logprob.hip)
     "spider_logprob_rows_bf16": (_i, [_vp, _i, _vp, _vp, _i] + [_vp] * 6 + [_i, _i, _vp]),
+    # calibrated MXFP4: the GPTQ sweep over one group of MX blocks (csrc/gptq.hip)
+    "spider_gptq_mxfp4_sweep_f32": (_i, [_vp] * 5 + [_i] * 4 + [_vp]),
     "spider_gemv_fm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "spider_gemv_swiglu_fm_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "spider_lm_head_argmax_fm_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),

@@ -156,6 +156,156 @@ def dequantize_mxfp4(blocks: torch.Tensor, scales: torch.Tensor, dtype=BF16) -> 
     return torch.ldexp(vals, (scales.to(torch.int32) - 127)[:, :, None]).reshape(N, K).to(dtype)
 
 
+FP4_MIDPOINTS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)     # between neighbouring FP4_VALUES; odd positions round up on a tie
+
+
+def gptq_prepare(W: torch.Tensor, H: torch.Tensor, damp: float = 0.01, who: str = "quantize_mxfp4_gptq"):
+    """Steps 1 - 3 of `quantize_mxfp4_gptq`: validate, clear dead inputs, damp. Returns fp64 copies (W [N, K], H [K, K]) on W's
+    device; a violation raises ValueError naming the argument."""
+    if not isinstance(W, torch.Tensor) or W.dim() != 2 or W.shape[1] % MX_BLOCK or W.numel() == 0 or not W.is_floating_point():
+        raise ValueError(f"{who}: W has to be a floating-point [N, K] matrix with K % {MX_BLOCK} == 0, got "
+                         f"{tuple(W.shape) if isinstance(W, torch.Tensor) else type(W)}")
+    N, K = W.shape
+    if not isinstance(H, torch.Tensor) or tuple(H.shape) != (K, K) or not H.is_floating_point():
+        raise ValueError(f"{who}: H has to be a floating-point [{K}, {K}] matrix (sum of x x^T over the layer's inputs), got "
+                         f"{tuple(H.shape) if isinstance(H, torch.Tensor) else type(H)}")
+    if isinstance(damp, bool) or not isinstance(damp, (int, float)) or not math.isfinite(damp) or damp <= 0:
+        raise ValueError(f"{who}: damp has to be a finite number > 0, but is {damp!r}")
+    Wd = W.detach().to(torch.float64).clone()
+    Hd = H.detach().to(device=W.device, dtype=torch.float64).clone()
+    if not bool(torch.isfinite(Wd).all()) or bool((Wd.abs() > 6.0 * 2.0 ** 125).any()):
+        raise ValueError(f"{who}: W: entries have to be finite and at most 6 * 2^125 in magnitude")
+    if not bool(torch.isfinite(Hd).all()):
+        raise ValueError(f"{who}: H: entries have to be finite")
+    if float((Hd - Hd.t()).abs().max()) > 1e-5 * float(Hd.abs().max()):
+        raise ValueError(f"{who}: H has to be symmetric")
+    d = torch.diagonal(Hd)
+    if bool((d < 0).any()):
+        raise ValueError(f"{who}: H: the diagonal of a sum of x x^T cannot be negative")
+    dead = d == 0
+    d[dead] = 1.0                      # (a view: writes H's diagonal)
+    Wd[:, dead] = 0.0
+    d += float(damp) * float(d.mean())
+    return Wd, Hd
+
+
+def gptq_factor(Hd: torch.Tensor, who: str = "quantize_mxfp4_gptq") -> torch.Tensor:
+    """U [K, K] fp64, upper triangular with H^-1 = U^T U (step 4), by cholesky -> cholesky_inverse -> cholesky(upper), on Hd's device"""
+    L, info = torch.linalg.cholesky_ex(Hd)
+    if int(info) != 0:
+        raise ValueError(f"{who}: H is not positive definite after damping (it has to be a sum of x x^T)")
+    U, info = torch.linalg.cholesky_ex(torch.cholesky_inverse(L), upper=True)
+    if int(info) != 0:
+        raise ValueError(f"{who}: H is too ill-conditioned to factor its inverse; raise damp")
+    return U
+
+
+def quantize_mxfp4_gptq(W: torch.Tensor, H: torch.Tensor, damp: float = 0.01, trace: Optional[dict] = None):
+    """Calibrated MXFP4 (GPTQ: Frantar et al. 2022, on MX blocks): W [N, K], H [K, K] = sum x x^T over the inputs the matrix sees
+    -> (blocks uint8 [N, K / 2], scales uint8 [N, K / 32]) in `quantize_mxfp4`'s layout. The codes are chosen column by column
+    along K; each column's rounding error is pushed into the columns not yet quantised, weighted by the inverse Hessian, so that
+    ||X (W - Q)^T|| shrinks where plain rounding minimises ||W - Q||. In fp64, every row independently:
+      1. W [N, K] with K % 32 == 0, H [K, K] finite and symmetric, damp > 0 (else ValueError naming the argument).
+      2. dead inputs: where H[k, k] == 0, H[k, k] = 1 and W[:, k] = 0.       3. H += damp * mean(diag H) * I.
+      4. U = the upper Cholesky factor of H^-1 (H^-1 = U^T U).
+      5. per block g (columns j = 32 g .. 32 g + 31), in order:
+         scale: `quantize_mxfp4`'s exponent rule on the amax of the block's CURRENT (already compensated) weights;
+         for i = 0 .. 31 in order: a = |w_i| / s, code by `quantize_mxfp4`'s midpoint rule (a > 6 can occur now and saturates at
+         code 7), sign bit from w_i, q = +-value * s;  e_i = (w_i - q) / U[j+i, j+i];  w_i' -= e_i U[j+i, j+i'] for i < i' <= 31;
+         then W[:, j+32:] -= E U[j:j+32, j+32:] with E = [e_0 .. e_31].
+    A diagonal H leaves nothing to compensate and returns `quantize_mxfp4(W)`'s bytes (a weight that is exactly -0.0 may come out
+    as +0.0); `dequantize_mxfp4` of the result is a bf16 matrix as before. What it costs: the plain weight error ||W - Q|| / ||W||
+    goes UP (11.4 % -> 13.5 % on N(0, 0.02^2) rows under correlated inputs), and on inputs unlike the calibration set the output
+    error can exceed round-to-nearest's. Pure torch; runs wherever W lives (`ops.gptq_mxfp4` is the device form in fp32).
+    trace: a dict that receives, per row, how close this fp64 run came to a decision another precision could take differently:
+    `mid_gap` [N] = min over the row's weights of |a - midpoint| / max(1, midpoint), and `mant_gap` [N] = min over the row's
+    non-zero blocks of |m - 0.75| (m the frexp mantissa of the block's amax)."""
+    Wd, Hd = gptq_prepare(W, H, damp)
+    U = gptq_factor(Hd)
+    N, K = Wd.shape
+    mids = torch.tensor(FP4_MIDPOINTS, dtype=torch.float64, device=Wd.device)
+    up = torch.tensor([i & 1 for i in range(7)], dtype=torch.bool, device=Wd.device)
+    table = torch.tensor(FP4_VALUES, dtype=torch.float64, device=Wd.device)
+    codes = torch.empty(N, K, dtype=torch.uint8, device=Wd.device)
+    scales = torch.empty(N, K // MX_BLOCK, dtype=torch.uint8, device=Wd.device)
+    E = torch.empty(N, MX_BLOCK, dtype=torch.float64, device=Wd.device)
+    mid_gap = torch.full((N,), float("inf"), dtype=torch.float64, device=Wd.device)
+    mant_gap = mid_gap.clone()
+    for g in range(K // MX_BLOCK):
+        j = g * MX_BLOCK
+        Wb = Wd[:, j:j + MX_BLOCK]
+        amax = Wb.abs().amax(dim=1)
+        m, e = torch.frexp(amax)
+        e = (e - 3 + (m > 0.75).to(e.dtype)).clamp(-125, 125)
+        e = torch.where(amax > 0, e, torch.zeros_like(e))
+        s = torch.ldexp(torch.ones_like(amax), e)
+        scales[:, g] = (e + 127).to(torch.uint8)
+        mant_gap = torch.minimum(mant_gap, torch.where(amax > 0, (m - 0.75).abs(), mant_gap))
+        for i in range(MX_BLOCK):
+            w = Wb[:, i].clone()
+            a = (w.abs() / s)[:, None]
+            c = (torch.where(up, a >= mids, a > mids)).sum(dim=1)
+            mid_gap = torch.minimum(mid_gap, ((a - mids).abs() / mids.clamp(min=1.0)).amin(dim=1))
+            q = torch.copysign(table[c] * s, w)
+            codes[:, j + i] = c.to(torch.uint8) | (torch.signbit(w).to(torch.uint8) << 3)
+            E[:, i] = (w - q) / U[j + i, j + i]
+            if i + 1 < MX_BLOCK:
+                Wb[:, i + 1:] -= E[:, i:i + 1] * U[j + i, j + i + 1:j + MX_BLOCK][None]
+        if j + MX_BLOCK < K:
+            Wd[:, j + MX_BLOCK:] -= E @ U[j:j + MX_BLOCK, j + MX_BLOCK:]
+    if trace is not None:
+        trace["mid_gap"], trace["mant_gap"] = mid_gap, mant_gap
+    codes = codes.reshape(N, K // 2, 2)
+    return (codes[:, :, 0] | (codes[:, :, 1] << 4)).contiguous(), scales.contiguous()
+
+
+def gptq_proxy_loss(W: torch.Tensor, Q: torch.Tensor, H: torch.Tensor) -> float:
+    """tr((W - Q) H (W - Q)^T) / tr(W H W^T) in fp64: the squared relative output error ||X (W - Q)^T||^2 / ||X W^T||^2 over the
+    inputs X that H = X^T X sums (the layer-wise objective GPTQ minimises)"""
+    Hd = H.detach().to(device=W.device, dtype=torch.float64)
+    Wd = W.detach().to(torch.float64)
+    D = Wd - Q.detach().to(device=W.device, dtype=torch.float64)
+    den = float(((Wd @ Hd) * Wd).sum())
+    return float(((D @ Hd) * D).sum()) / den if den > 0 else 0.0
+
+
+def resolve_calibration(calibration, vocab: int, max_len: int, weight_dtype: str = "bf16", lm_head_dtype: str = "bf16"):
+    """`calibration` of LlamaEngine, checked on the host: None (no calibration; returns None), or a dict with `input_ids` [n, S]
+    (integer, ids in [0, vocab), S <= max_len), optionally `attention_mask` [n, S] (LEFT padding, as in prefill_begin) and `damp`
+    (default 0.01). At least one of weight_dtype / lm_head_dtype has to be "mxfp4". A violation raises ValueError naming the
+    field. Returns dict(input_ids int64 [n, S], attention_mask int64 [n, S] or None, damp float, n_tokens int) on the host."""
+    if calibration is None:
+        return None
+    if not isinstance(calibration, dict):
+        raise ValueError(f"calibration has to be None or a dict with input_ids (and attention_mask, damp), but is {type(calibration).__name__}")
+    if "mxfp4" not in (weight_dtype, lm_head_dtype):
+        raise ValueError("calibration needs weight_dtype='mxfp4' or lm_head_dtype='mxfp4' (it chooses MXFP4 codes; FP8 and bf16 parts "
+                         "have nothing to calibrate)")
+    extra = sorted(set(calibration) - {"input_ids", "attention_mask", "damp"})
+    if extra:
+        raise ValueError(f"calibration: unknown field(s) {extra}; the fields are input_ids, attention_mask, damp")
+    ids = calibration.get("input_ids")
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64) or ids.numel() == 0:
+        raise ValueError("calibration: input_ids is required: a non-empty integer tensor [n, S]")
+    ids = ids.detach().cpu().to(torch.int64)
+    n, S = ids.shape
+    if int(ids.min()) < 0 or int(ids.max()) >= vocab:
+        raise ValueError(f"calibration: input_ids must be in [0, {vocab})")
+    if S > max_len:
+        raise ValueError(f"calibration: input_ids: length {S} exceeds max_len {max_len}")
+    am = calibration.get("attention_mask")
+    if am is not None:
+        if not isinstance(am, torch.Tensor) or tuple(am.shape) != (n, S):
+            raise ValueError(f"calibration: attention_mask must be [{n}, {S}]")
+        am = (am.detach().cpu() != 0).to(torch.int64)
+        if bool((am[:, 1:] < am[:, :-1]).any()) or bool((am[:, -1] == 0).any()):
+            raise ValueError("calibration: attention_mask must describe LEFT padding: zeros, then ones up to the last position of every row")
+    damp = calibration.get("damp", 0.01)
+    if isinstance(damp, bool) or not isinstance(damp, (int, float)) or not math.isfinite(damp) or damp <= 0:
+        raise ValueError(f"calibration: damp has to be a finite number > 0, but is {damp!r}")
+    return dict(input_ids=ids, attention_mask=am, damp=float(damp), n_tokens=int(am.sum()) if am is not None else n * S)
+
+
 @dataclass
 class LLMConfig:
     hidden: int
@@ -1001,7 +1151,7 @@ class LlamaEngine:
     MXFP4_FM_MAX_ROWS = 8
 
     def __init__(self, cfg: LLMConfig, weights: dict, device="cuda:0", max_batch: int = 1, max_len: int = 4096,
-                 weight_dtype: str = "bf16", lm_head_dtype: str = "bf16", batched_weight_stream: bool = False):
+                 weight_dtype: str = "bf16", calibration=None, lm_head_dtype: str = "bf16", batched_weight_stream: bool = False):
         """weight_dtype="fp8": weight-only FP8 for the decode weight stream. w_qkv, w_o, w_gu and w_down of every layer are
         quantised per output row (`quantize_fp8_rows`: OCP e4m3 with a power-of-two scale; embeddings, lm_head, norms and biases
         stay bf16) and the layer's bf16 matrices are REPLACED by the dequantised W_eff, which bf16 holds exactly. The engine then
@@ -1031,7 +1181,19 @@ class LlamaEngine:
         gemv_fm_w* (qkv, bias) -> attention -> gemv_fm_w* (o, res) -> rmsnorm -> gemv_swiglu_fm_w* -> gemv_fm_w* (down, res): the same
         function of W_eff as the bf16 fragment-major route, in another summation order and with the RMSNorm in a launch of its own
         instead of folded into the weights. The lm_head is not touched. Graph keys do not change; the default False adds no tensor
-        and changes no step."""
+        and changes no step.
+        calibration=dict(input_ids=[n, S], attention_mask=None, damp=0.01) (pass it by name: it sits behind weight_dtype, in front of
+        lm_head_dtype and batched_weight_stream, which stay the last two parameters; needs weight_dtype or lm_head_dtype "mxfp4";
+        `resolve_calibration` has the rules): the MXFP4 codes are chosen by `quantize_mxfp4_gptq` instead of round to nearest, on
+        the Hessians of what each matrix really sees when the engine runs these tokens (`_calibrate`: one sequential pass, every
+        layer calibrated behind the already quantised layers before it; ops.gptq_mxfp4, csrc/gptq.hip). Storage, kernels, graphs
+        and the "bf16 model on W_eff" property are unchanged -- only the bytes differ. `self.calibration` records method, n_tokens,
+        damp and, per quantised matrix, (layer, name, proxy_rtn, proxy_gptq) by `gptq_proxy_loss` (layer None: the lm_head). The
+        gain holds on inputs like the calibration set: the plain weight error goes up, inputs unlike the set can fare worse than
+        round to nearest (with fewer calibration tokens than a matrix has inputs the Hessians are rank-deficient and held-out
+        tokens DO fare worse: profiles/quant_quality_gptq_synthetic.txt), and no text-quality claim is made. FP8 parts keep `quantize_fp8_rows`. A calibrated head cannot be
+        quantised again (resize_token_embeddings / load_token_rows raise): build a new engine. The default None changes nothing:
+        no tensor, no kernel, no graph key."""
         self.weight_dtype = resolve_weight_dtype(weight_dtype)
         self.lm_head_dtype = resolve_lm_head_dtype(lm_head_dtype)
         self.batched_weight_stream = bool(batched_weight_stream)
@@ -1052,6 +1214,10 @@ class LlamaEngine:
             raise ValueError("weight_dtype='mxfp4' needs hidden, inter and n_q * head_dim to be multiples of 32 (one E8M0 scale per block of 32 weights)")
         if self.weight_dtype == "fp8" and (cfg.hidden % 16 or cfg.inter % 16 or (cfg.n_q * cfg.head_dim) % 16):
             raise ValueError("weight_dtype='fp8' needs hidden, inter and n_q * head_dim to be multiples of 16 (16 weights per 16-byte load)")
+        cal = resolve_calibration(calibration, cfg.vocab, max_len, self.weight_dtype, self.lm_head_dtype)
+        self.calibration = None
+        cal_layers = cal is not None and self.weight_dtype == "mxfp4"       # (their codes come from _calibrate, below)
+        self._cal_head = cal is not None and self.lm_head_dtype == "mxfp4"
         self.cfg, self.device = cfg, torch.device(device)
         self.max_batch, self.max_len = max_batch, max_len
         dv = self.device
@@ -1059,7 +1225,8 @@ class LlamaEngine:
         self.embed_w = g("model.embed_tokens.weight")
         self._head_tied = bool(cfg.tie_embeddings or "lm_head.weight" not in weights)
         self.lm_head = self.embed_w if self._head_tied else g("lm_head.weight")
-        self._quantize_head()
+        if not self._cal_head:
+            self._quantize_head()
         self.norm = g("model.norm.weight")
         self.layers = []
         for l in range(cfg.layers):
@@ -1078,12 +1245,15 @@ class LlamaEngine:
                     q, sc = quantize_fp8_rows(lw[k])
                     lw[k] = dequantize_fp8_rows(q, sc).contiguous()      # W_eff: what every bf16 kernel of this engine reads
                     lw[k + "_q8"], lw[k + "_s8"] = q.contiguous(), sc.contiguous()
-            elif self.weight_dtype == "mxfp4":
+            elif self.weight_dtype == "mxfp4" and not cal_layers:
                 for k in ("w_qkv", "w_o", "w_gu", "w_down"):
                     q, sc = quantize_mxfp4(lw[k])
                     lw[k] = dequantize_mxfp4(q, sc).contiguous()         # W_eff, as above
                     lw[k + "_q4"], lw[k + "_e4"] = q, sc
             self.layers.append(lw)
+        if cal is not None:
+            self._alloc()       # (the pass needs the rope table and cache set 0 as scratch)
+            self._calibrate(cal, cal_layers)
         # Batched decode (5..8 sequences per graph) streams a second, fragment-major copy of every decode weight (ops.repack_fm16:
         # 1 KiB contiguous per wave instruction of the skinny MFMA kernels). Memory is laid out for 288 GB of HBM: the copy
         # costs one more model size (15 GB for the 7B / 8B decoders) and buys 1.4 - 1.6x on the batched weight streams.
@@ -1103,13 +1273,17 @@ class LlamaEngine:
                         lw[k + "_q8fm"] = ops.repack_fm_w8(lw[k + "_q8"])
                     else:
                         lw[k + "_q4fm"], lw[k + "_e4fm"] = ops.repack_fm_w4(lw[k + "_q4"], lw[k + "_e4"])
-        self._alloc()
+        if cal is None:
+            self._alloc()
 
     def _quantize_head(self):
         """lm_head_dtype="fp8" / "mxfp4": quantise the head's source -- the embedding matrix of a tied configuration, else the head
         matrix itself, where both quantisers are fixed points in values -- and make `lm_head` its W_eff beside the bytes"""
         if self.lm_head_dtype == "bf16":
             return
+        if self._cal_head:
+            raise ValueError("the lm_head of this engine was calibrated (calibration=...): its codes depend on the calibration pass and "
+                             "cannot be derived again after the vocabulary changed; build a new engine")
         src = self.embed_w if self._head_tied else self.lm_head
         if self.lm_head_dtype == "fp8":
             q, sc = quantize_fp8_rows(src)
@@ -1123,7 +1297,7 @@ class LlamaEngine:
     # ------------------------------------------------------------------ construction helpers
     @classmethod
     def random_init(cls, cfg: LLMConfig, device="cuda:0", max_batch=1, max_len=4096, seed=0, std=0.02, weight_dtype="bf16",
-                    lm_head_dtype="bf16", batched_weight_stream=False):
+                    calibration=None, lm_head_dtype="bf16", batched_weight_stream=False):
         """Random N(0, std^2) weights of the architecture's true shapes, created directly in HBM
         (init scheme of modeling_llama3.py:405-414). Used by bench.py: timing is weight-value independent."""
         gen = torch.Generator(device=device).manual_seed(seed)
@@ -1149,15 +1323,16 @@ class LlamaEngine:
             w[p + "input_layernorm.weight"] = one(cfg.hidden)
             w[p + "post_attention_layernorm.weight"] = one(cfg.hidden)
         return cls(cfg, w, device, max_batch, max_len, weight_dtype=weight_dtype, lm_head_dtype=lm_head_dtype,
-                   batched_weight_stream=batched_weight_stream)
+                   batched_weight_stream=batched_weight_stream, calibration=calibration)
 
     @classmethod
-    def from_pretrained(cls, path: str, device="cuda:0", max_batch=1, max_len=4096, weight_dtype="bf16", lm_head_dtype="bf16",
-                        batched_weight_stream=False):
+    def from_pretrained(cls, path: str, device="cuda:0", max_batch=1, max_len=4096, weight_dtype="bf16", calibration=None,
+                        lm_head_dtype="bf16", batched_weight_stream=False):
         """Load an HF checkpoint directory: config.json + model.safetensors(.index.json + shards) or pytorch_model.bin
         (spider_amd/checkpoint.py). From a Qwen2.5-Omni directory only `thinker.model.*` / `thinker.lm_head.*` are read.
         weight_dtype="fp8" / "mxfp4" quantise the layer matrices at load, lm_head_dtype="fp8" / "mxfp4" the lm_head (see the
-        constructor); batched_weight_stream=True adds the fragment-major quantised copies for decode graphs of 5..8 rows."""
+        constructor); batched_weight_stream=True adds the fragment-major quantised copies for decode graphs of 5..8 rows;
+        calibration=dict(input_ids=...) chooses the MXFP4 codes by GPTQ on those tokens (see the constructor)."""
         from .checkpoint import load_state_dict, read_config
 
         def keep(k: str):
@@ -1165,9 +1340,87 @@ class LlamaEngine:
             return kk if kk.startswith(("model.", "lm_head.")) else None
         cfg = LLMConfig.from_hf_dict(read_config(path))
         eng = cls(cfg, load_state_dict(path, keep=keep), device, max_batch, max_len, weight_dtype=weight_dtype,
-                  lm_head_dtype=lm_head_dtype, batched_weight_stream=batched_weight_stream)
+                  lm_head_dtype=lm_head_dtype, batched_weight_stream=batched_weight_stream, calibration=calibration)
         eng.generation_config = read_generation_config(path)
         return eng
+
+    @torch.no_grad()
+    def _calibrate(self, cal: dict, cal_layers: bool):
+        """The sequential calibration pass behind `calibration=`: `_prefill`'s layer loop over ALL calibration rows, in chunks of at
+        most max_batch sequences with cache set 0 as scratch; the residual stream of every row is kept between layers. In front of
+        each matrix the Hessian H = sum x x^T of its input rows (fp64 sums on the device; rows that attention_mask pads do not
+        enter) is summed, the matrix is quantised by ops.gptq_mxfp4 and REPLACED by its W_eff with the bytes beside it, and the
+        stream moves on through the quantised matrix: later matrices are calibrated on what the earlier ones really produce.
+        cal_layers False (weight_dtype is not "mxfp4"): the layers run as they are and only the head is calibrated, on the
+        Hessian of rmsnorm(h_final, norm)."""
+        c, dv, B = self.cfg, self.device, self.max_batch
+        ids = cal["input_ids"].to(dv)
+        n, S = ids.shape
+        am = cal["attention_mask"]
+        am_d = am.to(dv).to(torch.int32) if am is not None else torch.ones(n, S, dtype=torch.int32, device=dv)
+        pos2d = (am_d.cumsum(-1) - 1).clamp(min=0).to(torch.int32).contiguous()
+        slot = torch.arange(S, dtype=torch.int32, device=dv)[None].expand(B, S).contiguous().view(-1)
+        kv_beg = (S - am_d.sum(-1)).to(torch.int32).contiguous()
+        has_pad = am is not None and bool((am == 0).any())
+        real = am_d.view(-1).bool() if has_pad else None
+        chunks = [(a, min(a + B, n)) for a in range(0, n, B)]
+        record = []
+
+        def hessian(x):
+            H = torch.zeros(x.shape[1], x.shape[1], dtype=torch.float64, device=dv)
+            xs = x[real] if real is not None else x
+            for a in range(0, xs.shape[0], 4096):
+                x64 = xs[a:a + 4096].double()
+                H.addmm_(x64.t(), x64)
+            return (H + H.t()) * 0.5
+
+        def quantise(W, x, layer, name):
+            H = hessian(x)
+            q, sc = ops.gptq_mxfp4(W, H, cal["damp"])
+            W_eff = dequantize_mxfp4(q, sc).contiguous()
+            rtn = dequantize_mxfp4(*quantize_mxfp4(W))
+            record.append((layer, name, gptq_proxy_loss(W, rtn, H), gptq_proxy_loss(W, W_eff, H)))
+            return W_eff, q, sc
+
+        def rows(fn, width):        # a row-wise stage over all sequences, chunk by chunk
+            out = torch.empty(n * S, width, dtype=BF16, device=dv)
+            for a, b in chunks:
+                out[a * S:b * S] = fn(a * S, b * S)
+            return out
+        h = self.embed_tokens(ids).view(n * S, -1)
+        k_cache, v_cache = self._kv(0)
+        for l, lw in enumerate(self.layers):
+            def put(k, x):
+                if cal_layers:
+                    lw[k], lw[k + "_q4"], lw[k + "_e4"] = quantise(lw[k], x, l, k)
+            x = rows(lambda a, b: ops.rmsnorm(h[a:b], lw["ln1"], c.eps), c.hidden)
+            put("w_qkv", x)
+            att = torch.empty(n * S, c.n_q * c.head_dim, dtype=BF16, device=dv)
+            for a, b in chunks:
+                nb = b - a
+                qkv = ops.gemm(x[a * S:b * S], lw["w_qkv"], bias=lw["b_qkv"])
+                q = torch.empty(nb, S, c.n_q, c.head_dim, dtype=BF16, device=dv)
+                ops.rope_kv_append(qkv, pos2d[a:b].contiguous().view(-1), slot[:nb * S], self.cos_sin, q, k_cache[l], v_cache[l], nb, S,
+                                   c.n_q, c.n_kv, c.head_dim)
+                att[a * S:b * S] = ops.attention_cache(q, k_cache[l], v_cache[l], Lk=S, causal=True, kv_off=0,
+                                                       kv_beg=kv_beg[a:b].contiguous() if has_pad else None).view(nb * S, -1)
+            put("w_o", att)
+            h = rows(lambda a, b: ops.gemm(att[a:b], lw["w_o"], res=h[a:b]), c.hidden)
+            x = rows(lambda a, b: ops.rmsnorm(h[a:b], lw["ln2"], c.eps), c.hidden)
+            put("w_gu", x)
+            if _FUSE_SWIGLU:
+                act = rows(lambda a, b: ops.gemm(x[a:b], lw["w_gu"], act="swiglu"), c.inter)
+            else:
+                act = rows(lambda a, b: ops.swiglu(ops.gemm(x[a:b], lw["w_gu"])), c.inter)
+            put("w_down", act)
+            h = rows(lambda a, b: ops.gemm(act[a:b], lw["w_down"], res=h[a:b]), c.hidden)
+        if self._cal_head:
+            x = rows(lambda a, b: ops.rmsnorm(h[a:b], self.norm, c.eps), c.hidden)
+            src = self.embed_w if self._head_tied else self.lm_head
+            W_eff, q, sc = quantise(src, x, None, "lm_head")
+            self.lm_head, self.lm_head_q4, self.lm_head_e4 = W_eff, q, sc
+        k_cache.zero_(); v_cache.zero_()        # (scratch use over: the cache a new engine hands out is zero)
+        self.calibration = dict(method="gptq", n_tokens=cal["n_tokens"], damp=cal["damp"], matrices=record)
 
     def _alloc(self):
         c, dv, B, T = self.cfg, self.device, self.max_batch, self.max_len

@@ -963,6 +963,102 @@ def logprob_rows(logits, targets, V: Optional[int] = None, logits_ref=None) -> d
     return out
 
 
+GPTQ_MAX_GROUP_BLOCKS = 4     # MX blocks per launch of the sweep kernel (its LDS holds a [128, 128] fp32 block of U)
+GPTQ_GROUP_BLOCKS = 4         # the driver's default group width
+_GPTQ_DEVICE_LINALG = {}      # device index -> does this torch build factor fp64 matrices on the device
+
+
+def gptq_factor_where(device) -> str:
+    """"device" when this torch build runs cholesky / cholesky_inverse in fp64 on `device` (probed once on a 2 x 2 matrix), else
+    "host": where `gptq_mxfp4` computes the factor U"""
+    key = torch.device(device).index or 0
+    if key not in _GPTQ_DEVICE_LINALG:
+        try:
+            a = torch.eye(2, dtype=torch.float64, device=device) * 2.0
+            L = torch.linalg.cholesky(a)
+            ok = bool(torch.isfinite(torch.linalg.cholesky(torch.cholesky_inverse(L), upper=True)).all())
+        except RuntimeError:
+            ok = False
+        _GPTQ_DEVICE_LINALG[key] = ok
+    return "device" if _GPTQ_DEVICE_LINALG[key] else "host"
+
+
+def gptq_mxfp4_sweep(Wt, U, blocks, scales, Et, j0: int, nblocks: int):
+    """One launch of csrc/gptq.hip: quantise the MX blocks of columns [j0, j0 + 32 nblocks) of every row of the K-major working
+    copy Wt [K, N] fp32 with the group's diagonal block of U [K, K] fp32; writes blocks [N, K / 2], scales [N, K / 32] and the
+    first 32 nblocks rows of Et [>= 32 nblocks, N] fp32 (E transposed). The columns behind the group are the caller's."""
+    _chk(Wt, torch.float32, "Wt"); _chk(U, torch.float32, "U"); _chk(Et, torch.float32, "Et")
+    _chk(blocks, torch.uint8, "blocks"); _chk(scales, torch.uint8, "scales")
+    if Wt.dim() != 2 or Wt.shape[0] % 32 or Wt.shape[0] < 32 or Wt.shape[1] < 1:
+        raise ValueError(f"Wt: expected a K-major working copy [K, N] with K % 32 == 0, got {tuple(Wt.shape)}")
+    K, N = Wt.shape
+    if tuple(U.shape) != (K, K) or tuple(blocks.shape) != (N, K // 2) or tuple(scales.shape) != (N, K // 32):
+        raise ValueError(f"expected U [{K}, {K}], blocks [{N}, {K // 2}] and scales [{N}, {K // 32}], got {tuple(U.shape)}, "
+                         f"{tuple(blocks.shape)} and {tuple(scales.shape)}")
+    if not 1 <= nblocks <= GPTQ_MAX_GROUP_BLOCKS or j0 < 0 or j0 % 32 or j0 + 32 * nblocks > K:
+        raise ValueError(f"group [{j0}, {j0} + 32 * {nblocks}) has to hold 1..{GPTQ_MAX_GROUP_BLOCKS} whole MX blocks within K = {K}")
+    if Et.dim() != 2 or Et.shape[1] != N or Et.shape[0] < 32 * nblocks:
+        raise ValueError(f"Et: expected [>= {32 * nblocks}, {N}], got {tuple(Et.shape)}")
+    _lib.call("spider_gptq_mxfp4_sweep_f32", _p(Wt), _p(U), _p(blocks), _p(scales), _p(Et), N, K, j0, nblocks, _stream())
+
+
+def gptq_mxfp4(W, H, damp: float = 0.01, group_blocks: Optional[int] = None, timing: Optional[dict] = None):
+    """`llm.quantize_mxfp4_gptq(W, H, damp)` on the device: W [N, K] (any float dtype) and H [K, K] on the current HIP device ->
+    (blocks uint8 [N, K / 2], scales uint8 [N, K / 32]) on the device, in `quantize_mxfp4`'s layout.
+    Validation, dead inputs and damping are the definition's (`llm.gptq_prepare`, fp64, on the device). The factor U comes from
+    `llm.gptq_factor` in fp64 -- on the device when this torch build provides the fp64 factorisations there, else on the host
+    (`gptq_factor_where`) -- and is rounded to fp32 once. The sweep then runs in fp32: one launch of csrc/gptq.hip per group of
+    `group_blocks` MX blocks (default GPTQ_GROUP_BLOCKS; a narrower tail group when K / 32 is no multiple), and between launches
+    the columns behind the group take Wt[behind] -= U[group, behind]^T Et as one true-fp32 `addmm_` (TF32 off). The bytes equal
+    the definition's except where fp32 rounding decides a tie (a weight within ~1e-6 relative of a rounding midpoint, an amax
+    within that of a binade's 0.75); group_blocks changes the fp32 summation order of the compensation and nothing else.
+    timing: a dict that receives the seconds spent in prepare / factor / sweep (each behind a device synchronisation)."""
+    from .llm import gptq_factor, gptq_prepare
+    import time
+    if not isinstance(W, torch.Tensor) or not W.is_cuda:
+        raise ValueError("W: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
+    if W.device.index != torch.cuda.current_device():
+        raise ValueError(f"W: tensor lives on {W.device} but the current device is cuda:{torch.cuda.current_device()}")
+    gb = GPTQ_GROUP_BLOCKS if group_blocks is None else int(group_blocks)
+    if not 1 <= gb <= GPTQ_MAX_GROUP_BLOCKS:
+        raise ValueError(f"group_blocks={group_blocks} has to be in 1..{GPTQ_MAX_GROUP_BLOCKS}")
+    dv = W.device
+
+    def lap(name, t0):
+        if timing is not None:
+            torch.cuda.synchronize(dv)
+            timing[name] = timing.get(name, 0.0) + time.perf_counter() - t0
+        return time.perf_counter()
+    t = time.perf_counter()
+    Wd, Hd = gptq_prepare(W, H, damp, who="gptq_mxfp4")
+    t = lap("prepare", t)
+    where = gptq_factor_where(dv)
+    U = (gptq_factor(Hd, who="gptq_mxfp4") if where == "device" else gptq_factor(Hd.cpu(), who="gptq_mxfp4").to(dv)).float().contiguous()
+    del Hd
+    if timing is not None:
+        timing["factor_where"] = where
+    t = lap("factor", t)
+    N, K = Wd.shape
+    Wt = Wd.t().to(torch.float32).contiguous()          # the K-major working copy [K, N]
+    del Wd
+    blocks = torch.empty(N, K // 2, dtype=torch.uint8, device=dv)
+    scales = torch.empty(N, K // 32, dtype=torch.uint8, device=dv)
+    Et = torch.empty(32 * gb, N, dtype=torch.float32, device=dv)
+    tf32 = torch.backends.cuda.matmul.allow_tf32
+    torch.backends.cuda.matmul.allow_tf32 = False
+    try:
+        for j0 in range(0, K, 32 * gb):
+            nb = min(gb, (K - j0) // 32)
+            j1 = j0 + 32 * nb
+            gptq_mxfp4_sweep(Wt, U, blocks, scales, Et, j0, nb)
+            if j1 < K:
+                Wt[j1:].addmm_(U[j0:j1, j1:].t(), Et[:32 * nb], alpha=-1.0)
+    finally:
+        torch.backends.cuda.matmul.allow_tf32 = tf32
+    lap("sweep", t)
+    return blocks, scales
+
+
 def rope_kv_append(qkv, pos, slot, cos_sin, q_out, k_cache, v_cache, B, S, n_q, n_kv, d, mrope_section=None):
     """pos [B*S] int32, or [3, B*S] with mrope_section=(t, h, w) rotary pairs per component (Qwen2.5-Omni: 16, 24, 24)."""
     _chk(qkv, BF16, "qkv"); _chk(pos, torch.int32, "pos"); _chk(slot, torch.int32, "slot")

@@ -560,8 +560,22 @@ def _(logits, targets, V, logits_ref=None):
     return f32(rows), f32(rows), i32(rows), f32(rows), f32(n), i32(n)
 
 
+# ------------------------------------------------------------------------------------------ calibrated MXFP4 (GPTQ on MX blocks)
+@_op("gptq_mxfp4")
+def gptq_mxfp4(W: torch.Tensor, H: torch.Tensor, damp: float = 0.01) -> tuple[torch.Tensor, torch.Tensor]:
+    """`llm.quantize_mxfp4_gptq(W, H, damp)` on the device (ops.gptq_mxfp4: fp64 factor, fp32 sweep kernel of csrc/gptq.hip):
+    W [N, K], H [K, K] -> (blocks uint8 [N, K / 2], scales uint8 [N, K / 32]) in `quantize_mxfp4`'s layout"""
+    return ops.gptq_mxfp4(W, H, damp)
+
+
+@gptq_mxfp4.register_fake
+def _(W, H, damp=0.01):
+    N, K = W.shape
+    return W.new_empty(N, K // 2, dtype=torch.uint8), W.new_empty(N, K // 32, dtype=torch.uint8)
+
+
 # the export list of SURVEY.md section 8b; the in-place decode-bookkeeping ops, the FP8 and MXFP4 GEMVs (row-major and fragment-major) and lm_heads, the safety-checker
-# ops and the audio and image feature ops above are listed apart
+# ops, the audio and image feature ops, the scoring op and the calibration op above are listed apart
 SAFETY_OP_NAMES = ("clip_preprocess", "safety_decide", "image_blackout_")
 AUDIO_OP_NAMES = ("logmel",)
 IMAGE_OP_NAMES = ("qwen_image_patches",)
@@ -573,5 +587,6 @@ DECODE_OP_NAMES = ("ngram_ban_", "decode_advance_seen_ngram_")
 SPEC_OP_NAMES = ("attn_verify", "prompt_lookup_draft_", "spec_advance_draft_")
 ASSIST_OP_NAMES = ("spec_assist_push_", "spec_assist_advance_")
 SCORE_OP_NAMES = ("logprob_rows",)
+GPTQ_OP_NAMES = ("gptq_mxfp4",)
 OP_NAMES = ("rmsnorm", "rope_qk_", "attn_decode", "attn_prefill_causal", "swiglu", "linear_bf16", "lm_head_argmax", "groupnorm_silu",
             "conv2d_nhwc", "attn_self", "attn_cross_kv77", "attn_consistent", "geglu", "cfg_step")
