@@ -53,6 +53,8 @@ def test_rmsnorm(ops, dev, rows, H):
     close(y2, rmsnorm(hsum.float(), w.float(), 1e-6), 1e-2, 1e-2, "rmsnorm+res")
 
 
+# (8, 64, 18944) takes the MFMA route (skinny_gemm_kernel: B >= 5 and K % 64 == 0), not gemv_kernel with the activations read
+# through L2; that route, at 2..8 rows, is in tests/test_gemv_routes_gpu.py
 @pytest.mark.parametrize("B,N,K", [(1, 4608, 3584), (1, 3584, 18944), (2, 512, 4096), (8, 130, 1024), (3, 7, 64), (8, 64, 18944)])
 def test_gemv(ops, dev, B, N, K):
     from oracle.llama import rmsnorm
