@@ -44,6 +44,7 @@ from __future__ import annotations
 
 import os
 import math
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
 
@@ -1103,6 +1104,39 @@ class StoppingCriteriaSub:
         return False
 
 
+# The weight routes of a decode step. A route is one encoding of the weights and the ops that stream it: the layer GEMV, the gate-up
+# GEMV with SwiGLU, the lm_head arg-max and its form with logits processors (the fragment-major quantised copies exist for the layers
+# only). `suffixes` name where the encoding lives: layer key "w_qkv" / "w_o" / "w_gu" / "w_down" + suffix, engine attribute "lm_head" +
+# suffix. The ops are named, not bound: a step looks them up in `ops` when it runs. fm: the fragment-major op families, which take the
+# output rows N (the lm_head: V) behind x and no norm_w= (the bf16 copies carry the norm's weight and take norm_eps=).
+_Route = namedtuple("_Route", "gemv swiglu head head_proc suffixes fm")
+ROUTES = {
+    "bf16":     _Route("gemv", "gemv_swiglu", "lm_head_argmax", "lm_head_argmax_proc", ("",), False),
+    "bf16_fm":  _Route("gemv_fm", "gemv_swiglu_fm", "lm_head_argmax_fm", "lm_head_argmax_fm_proc", ("_fm",), True),
+    "fp8":      _Route("gemv_w8", "gemv_swiglu_w8", "lm_head_argmax_w8", "lm_head_argmax_proc_w8", ("_q8", "_s8"), False),
+    "mxfp4":    _Route("gemv_w4", "gemv_swiglu_w4", "lm_head_argmax_w4", "lm_head_argmax_proc_w4", ("_q4", "_e4"), False),
+    "fp8_fm":   _Route("gemv_fm_w8", "gemv_swiglu_fm_w8", None, None, ("_q8fm", "_s8"), True),
+    "mxfp4_fm": _Route("gemv_fm_w4", "gemv_swiglu_fm_w4", None, None, ("_q4fm", "_e4fm"), True),
+}
+# How the RMSNorm in front of qkv, gate-up and the lm_head is served: norm_w= / eps= of the GEMV, folded into the weights (norm_eps=),
+# or ops.rmsnorm into st["xn"] as a launch of its own
+NORM_ARG, NORM_FOLDED, NORM_LAUNCH = "arg", "folded", "launch"
+# What a quantised weight format brings: its quantiser pair, and where `LlamaEngine._decode_route` reads its row ranges (attributes of
+# the engine: measured crossovers; of `ops`: what the kernels exist for) and the LDS test of its fused norm
+_Quant = namedtuple("_Quant", "quantize dequantize rows fm_rows head_rows op_rows norm_fits")
+QUANT = {
+    "fp8":   _Quant(quantize_fp8_rows, dequantize_fp8_rows, "FP8_MAX_ROWS", "FP8_FM_MAX_ROWS", "LM_HEAD_FP8_MAX_ROWS", "W8_MAX_ROWS", "w8_norm_fits"),
+    "mxfp4": _Quant(quantize_mxfp4, dequantize_mxfp4, "MXFP4_MAX_ROWS", "MXFP4_FM_MAX_ROWS", "LM_HEAD_MXFP4_MAX_ROWS", "W4_MAX_ROWS", "w4_norm_fits"),
+}
+
+
+def quantize_weight(W: torch.Tensor, fmt: str):
+    """W -> (W_eff, q, scales) in weight format fmt ("fp8" / "mxfp4"): the bytes and what they decode to, the bf16 matrix every bf16
+    kernel of a quantised engine reads"""
+    q, sc = QUANT[fmt].quantize(W)
+    return QUANT[fmt].dequantize(q, sc).contiguous(), q.contiguous(), sc.contiguous()
+
+
 class LlamaEngine:
     DECODE_ROWS = 8     # sequences per decode graph (lm_head / split-KV workspaces are sized for 8)
     # From this many sequences on the decode GEMVs run as skinny MFMA GEMMs on fragment-major weight copies (SPIDER_DECODE_FM_MIN).
@@ -1240,16 +1274,10 @@ class LlamaEngine:
                 w_gu=torch.cat([g(p + "mlp.gate_proj.weight"), g(p + "mlp.up_proj.weight")], 0).contiguous(),
                 w_down=g(p + "mlp.down_proj.weight"),
                 ln1=g(p + "input_layernorm.weight"), ln2=g(p + "post_attention_layernorm.weight"))
-            if self.weight_dtype == "fp8":
-                for k in ("w_qkv", "w_o", "w_gu", "w_down"):
-                    q, sc = quantize_fp8_rows(lw[k])
-                    lw[k] = dequantize_fp8_rows(q, sc).contiguous()      # W_eff: what every bf16 kernel of this engine reads
-                    lw[k + "_q8"], lw[k + "_s8"] = q.contiguous(), sc.contiguous()
-            elif self.weight_dtype == "mxfp4" and not cal_layers:
-                for k in ("w_qkv", "w_o", "w_gu", "w_down"):
-                    q, sc = quantize_mxfp4(lw[k])
-                    lw[k] = dequantize_mxfp4(q, sc).contiguous()         # W_eff, as above
-                    lw[k + "_q4"], lw[k + "_e4"] = q, sc
+            if self.weight_dtype != "bf16" and not cal_layers:
+                sq, ss = ROUTES[self.weight_dtype].suffixes
+                for k in ("w_qkv", "w_o", "w_gu", "w_down"):     # lw[k] becomes W_eff: what every bf16 kernel of this engine reads
+                    lw[k], lw[k + sq], lw[k + ss] = quantize_weight(lw[k], self.weight_dtype)
             self.layers.append(lw)
         if cal is not None:
             self._alloc()       # (the pass needs the rope table and cache set 0 as scratch)
@@ -1285,14 +1313,9 @@ class LlamaEngine:
             raise ValueError("the lm_head of this engine was calibrated (calibration=...): its codes depend on the calibration pass and "
                              "cannot be derived again after the vocabulary changed; build a new engine")
         src = self.embed_w if self._head_tied else self.lm_head
-        if self.lm_head_dtype == "fp8":
-            q, sc = quantize_fp8_rows(src)
-            self.lm_head = dequantize_fp8_rows(q, sc).contiguous()
-            self.lm_head_q8, self.lm_head_s8 = q.contiguous(), sc.contiguous()
-        else:
-            q, sc = quantize_mxfp4(src)
-            self.lm_head = dequantize_mxfp4(q, sc).contiguous()
-            self.lm_head_q4, self.lm_head_e4 = q.contiguous(), sc.contiguous()
+        self.lm_head, q, sc = quantize_weight(src, self.lm_head_dtype)
+        for suffix, t in zip(ROUTES[self.lm_head_dtype].suffixes, (q, sc)):
+            setattr(self, "lm_head" + suffix, t)
 
     # ------------------------------------------------------------------ construction helpers
     @classmethod
@@ -1576,43 +1599,26 @@ class LlamaEngine:
         hs = st.get("hidden_buf")
         if hs is not None:
             hs[0].copy_(h)
-        fm = self.fm_batch and B >= self.FM_MIN_BATCH
-        # FP8 engines: up to FP8_MAX_ROWS rows the four layer GEMVs stream the e4m3 bytes (the lm_head follows lm_head_dtype: _lm_head_step)
-        w8 = self.weight_dtype == "fp8" and B <= min(self.FP8_MAX_ROWS, ops.W8_MAX_ROWS)
-        fuse_norm = not fm and B < 5      # the row-major GEMV folds the RMSNorm for up to 4 rows; the skinny MFMA GEMM (fm) carries it in its weights
-        w8_fuse = w8 and ops.w8_norm_fits(B, c.hidden)     # (a hidden size beyond the kernel's LDS budget: RMSNorm in its own launch)
-        # MXFP4 engines: the same four GEMVs on the e2m1 bytes and their block scales, up to MXFP4_MAX_ROWS rows
-        w4 = self.weight_dtype == "mxfp4" and B <= min(self.MXFP4_MAX_ROWS, ops.W4_MAX_ROWS)
-        w4_fuse = w4 and ops.w4_norm_fits(B, c.hidden)
-        # batched_weight_stream engines: above those ranges, up to *_FM_MAX_ROWS rows, the same bytes in fragment-major order (csrc/gemv_qfm.hip)
-        q8fm = self.batched_weight_stream and self.weight_dtype == "fp8" and not w8 and B <= min(self.FP8_FM_MAX_ROWS, ops.QFM_MAX_ROWS)
-        q4fm = self.batched_weight_stream and self.weight_dtype == "mxfp4" and not w4 and B <= min(self.MXFP4_FM_MAX_ROWS, ops.QFM_MAX_ROWS)
-        lookup = st.get("lookup")       # prompt-lookup verify step: the layer loop below at B = R rows, attention under the causal rule
+        layer, norm, *head = self._decode_route(B)
+        route = ROUTES[layer]
+
+        def proj(op, lw, k, x, N=None, norm_key=None, **kw):
+            """one layer GEMV on this step's route: ops.<op> on the route's encoding of lw[k]; norm_key: behind that RMSNorm"""
+            if norm_key is not None and norm == NORM_ARG:
+                kw.update(norm_w=lw[norm_key], eps=c.eps)
+            elif norm_key is not None and norm == NORM_FOLDED:
+                kw["norm_eps"] = c.eps
+            elif norm_key is not None:
+                x = ops.rmsnorm(x, lw[norm_key], c.eps, out=st["xn"])
+            rows = (N,) if route.fm and N is not None else ()
+            return getattr(ops, op)(*(lw[k + s] for s in route.suffixes), x, *rows, **kw)
+        lookup = st.get("lookup")     # prompt-lookup verify step: the layer loop below at B = R rows, attention under the causal rule
         # a step of an assisted round (`_assist_round`: the target's verify step, the draft engine's two-row and single-row steps): it
         # ends behind the lm_head, the round's own launches move the cursors; more than one row are rows of ONE sequence, as above
         assist = st.get("assist")
         one_seq = lookup is not None or (assist is not None and B > 1)
         for l, lw in enumerate(self.layers):
-            if q8fm:
-                ops.gemv_fm_w8(lw["w_qkv_q8fm"], lw["w_qkv_s8"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), lw["w_qkv"].shape[0],
-                               bias=lw["b_qkv"], out=st["qkv"])
-            elif q4fm:
-                ops.gemv_fm_w4(lw["w_qkv_q4fm"], lw["w_qkv_e4fm"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), lw["w_qkv"].shape[0],
-                               bias=lw["b_qkv"], out=st["qkv"])
-            elif w8 and w8_fuse:
-                ops.gemv_w8(lw["w_qkv_q8"], lw["w_qkv_s8"], h, bias=lw["b_qkv"], norm_w=lw["ln1"], eps=c.eps, out=st["qkv"])
-            elif w8:
-                ops.gemv_w8(lw["w_qkv_q8"], lw["w_qkv_s8"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), bias=lw["b_qkv"], out=st["qkv"])
-            elif w4 and w4_fuse:
-                ops.gemv_w4(lw["w_qkv_q4"], lw["w_qkv_e4"], h, bias=lw["b_qkv"], norm_w=lw["ln1"], eps=c.eps, out=st["qkv"])
-            elif w4:
-                ops.gemv_w4(lw["w_qkv_q4"], lw["w_qkv_e4"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), bias=lw["b_qkv"], out=st["qkv"])
-            elif fuse_norm:
-                ops.gemv(lw["w_qkv"], h, bias=lw["b_qkv"], norm_w=lw["ln1"], eps=c.eps, out=st["qkv"])
-            elif fm:
-                ops.gemv_fm(lw["w_qkv_fm"], h, lw["w_qkv"].shape[0], bias=lw["b_qkv"], out=st["qkv"], norm_eps=c.eps)
-            else:
-                ops.gemv(lw["w_qkv"], ops.rmsnorm(h, lw["ln1"], c.eps, out=st["xn"]), bias=lw["b_qkv"], out=st["qkv"])
+            proj(route.gemv, lw, "w_qkv", h, lw["w_qkv"].shape[0], norm_key="ln1", bias=lw["b_qkv"], out=st["qkv"])
             if one_seq:     # the B rows are ONE sequence's token and its drafts: R appended K / V rows, row r sees r more of them
                 ops.rope_kv_append(st["qkv"], st["pos"], st["slot"], self.cos_sin, st["q"], k_cache[l], v_cache[l],
                                    1, B, c.n_q, c.n_kv, c.head_dim)
@@ -1626,58 +1632,28 @@ class LlamaEngine:
                                    B, 1, c.n_q, c.n_kv, c.head_dim)
                 ops.attn_decode(st["q"], k_cache[l], v_cache[l], st["kv_end"], kv_beg=st["kv_beg"],
                                 nsplit=st["nsplit"], ws=st["attn_ws"], out=st["attn"])
-            if q8fm:
-                h1 = ops.gemv_fm_w8(lw["w_o_q8fm"], lw["w_o_s8"], st["attn"], c.hidden, res=h, out=st["h1"])
-                ops.gemv_swiglu_fm_w8(lw["w_gu_q8fm"], lw["w_gu_s8"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
-                h = ops.gemv_fm_w8(lw["w_down_q8fm"], lw["w_down_s8"], st["act"], c.hidden, res=h1, out=st["h2"][l & 1])
-            elif q4fm:
-                h1 = ops.gemv_fm_w4(lw["w_o_q4fm"], lw["w_o_e4fm"], st["attn"], c.hidden, res=h, out=st["h1"])
-                ops.gemv_swiglu_fm_w4(lw["w_gu_q4fm"], lw["w_gu_e4fm"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
-                h = ops.gemv_fm_w4(lw["w_down_q4fm"], lw["w_down_e4fm"], st["act"], c.hidden, res=h1, out=st["h2"][l & 1])
-            elif w8:
-                h1 = ops.gemv_w8(lw["w_o_q8"], lw["w_o_s8"], st["attn"], res=h, out=st["h1"])
-                if w8_fuse:
-                    ops.gemv_swiglu_w8(lw["w_gu_q8"], lw["w_gu_s8"], h1, norm_w=lw["ln2"], eps=c.eps, out=st["act"])
-                else:
-                    ops.gemv_swiglu_w8(lw["w_gu_q8"], lw["w_gu_s8"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
-                h = ops.gemv_w8(lw["w_down_q8"], lw["w_down_s8"], st["act"], res=h1, out=st["h2"][l & 1])
-            elif w4:
-                h1 = ops.gemv_w4(lw["w_o_q4"], lw["w_o_e4"], st["attn"], res=h, out=st["h1"])
-                if w4_fuse:
-                    ops.gemv_swiglu_w4(lw["w_gu_q4"], lw["w_gu_e4"], h1, norm_w=lw["ln2"], eps=c.eps, out=st["act"])
-                else:
-                    ops.gemv_swiglu_w4(lw["w_gu_q4"], lw["w_gu_e4"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
-                h = ops.gemv_w4(lw["w_down_q4"], lw["w_down_e4"], st["act"], res=h1, out=st["h2"][l & 1])
-            elif fm:
-                h1 = ops.gemv_fm(lw["w_o_fm"], st["attn"], c.hidden, res=h, out=st["h1"])
-                ops.gemv_swiglu_fm(lw["w_gu_fm"], h1, out=st["act"], norm_eps=c.eps)
-                h = ops.gemv_fm(lw["w_down_fm"], st["act"], c.hidden, res=h1, out=st["h2"][l & 1])
-            else:
-                h1 = ops.gemv(lw["w_o"], st["attn"], res=h, out=st["h1"])
-                if fuse_norm:
-                    ops.gemv_swiglu(lw["w_gu"], h1, norm_w=lw["ln2"], eps=c.eps, out=st["act"])
-                else:
-                    ops.gemv_swiglu(lw["w_gu"], ops.rmsnorm(h1, lw["ln2"], c.eps, out=st["xn"]), out=st["act"])
-                h = ops.gemv(lw["w_down"], st["act"], res=h1, out=st["h2"][l & 1])
+            h1 = proj(route.gemv, lw, "w_o", st["attn"], c.hidden, res=h, out=st["h1"])
+            proj(route.swiglu, lw, "w_gu", h1, norm_key="ln2", out=st["act"])
+            h = proj(route.gemv, lw, "w_down", st["act"], c.hidden, res=h1, out=st["h2"][l & 1])
             if hs is not None:
                 hs[l + 1].copy_(h)
         if assist is not None:      # the model's token behind every row; pushes / advance follow in `_assist_round`
-            self._lm_head_step(st, h, st["next_ids"], None, None, fm)
+            self._lm_head_step(st, h, st["next_ids"], None, None, head)
             return
         if lookup is not None:      # the model's token behind every row, then accept / append / advance / draft in one launch
-            self._lm_head_step(st, h, st["next_ids"], None, None, fm)
+            self._lm_head_step(st, h, st["next_ids"], None, None, head)
             ops.spec_advance_draft(lookup, st["hist"], st["n_hist"])
             return
         if st.get("beam") is not None:      # beam search: the raw logits of the B * K rows go to the beam step instead of an arg-max
-            self._lm_head_step(st, h, st["beam"]["lm_ids"], st["logits"], None, fm)
+            self._lm_head_step(st, h, st["beam"]["lm_ids"], st["logits"], None, head)
             self._beam_step(st)
             return
         proc = st.get("proc")      # logits processors in the arg-max epilogue (their parameters are read from the state's buffers)
         if st.get("sample") is not None:    # sampling: the raw logits go to the sampling step, which applies the processors itself
-            self._lm_head_step(st, h, st["sample"]["lm_ids"], st["logits"], None, fm)
+            self._lm_head_step(st, h, st["sample"]["lm_ids"], st["logits"], None, head)
             self._sample_step(st)
         else:
-            self._lm_head_step(st, h, st["next_ids"], st.get("logits"), proc, fm)
+            self._lm_head_step(st, h, st["next_ids"], st.get("logits"), proc, head)
         if hs is not None:  # HF reports the normed state as the last hidden state (modeling_llama3.py:619-623)
             ops.rmsnorm(h, self.norm, c.eps, out=hs[c.layers])
         # advance the device-side cursors and append the token to the on-device history (index math only, one launch)
@@ -1690,37 +1666,50 @@ class LlamaEngine:
         else:
             ops.decode_advance(st["next_ids"], st["cur_ids"], st["pos"], st["slot"], st["kv_end"], st["hist"], st["n_hist"])
 
-    def _lm_head_step(self, st: dict, h: torch.Tensor, out_ids: torch.Tensor, logits: Optional[torch.Tensor], proc: Optional[dict],
-                      fm: bool):
-        """The lm_head launch of a decode step: final norm + lm_head + arg-max (through `proc` when given) of the residual stream h
-        into out_ids, raw logits into `logits` when given. Engines with a quantised head stream its bytes up to
-        LM_HEAD_FP8_MAX_ROWS / LM_HEAD_MXFP4_MAX_ROWS rows (csrc/lm_head_wq.hip); everything else is the bf16 route on `lm_head`:
-        fragment-major when `fm`, else row-major."""
-        c, B, ws = self.cfg, st["B"], st["lm_ws"]
-        if self.lm_head_dtype == "fp8" and B <= min(self.LM_HEAD_FP8_MAX_ROWS, ops.LM_HEAD_Q_MAX_ROWS):
-            fuse = ops.w8_norm_fits(B, c.hidden)    # (a hidden size beyond the kernel's LDS budget: RMSNorm in its own launch)
-            x, nw = (h, self.norm) if fuse else (ops.rmsnorm(h, self.norm, c.eps, out=st["xn"]), None)
-            if proc is not None:
-                ops.lm_head_argmax_proc_w8(self.lm_head_q8, self.lm_head_s8, x, proc, norm_w=nw, eps=c.eps, out_ids=out_ids, ws=ws,
-                                           logits=logits)
-            else:
-                ops.lm_head_argmax_w8(self.lm_head_q8, self.lm_head_s8, x, norm_w=nw, eps=c.eps, out_ids=out_ids, ws=ws, logits=logits)
-        elif self.lm_head_dtype == "mxfp4" and B <= min(self.LM_HEAD_MXFP4_MAX_ROWS, ops.LM_HEAD_Q_MAX_ROWS):
-            fuse = ops.w4_norm_fits(B, c.hidden)
-            x, nw = (h, self.norm) if fuse else (ops.rmsnorm(h, self.norm, c.eps, out=st["xn"]), None)
-            if proc is not None:
-                ops.lm_head_argmax_proc_w4(self.lm_head_q4, self.lm_head_e4, x, proc, norm_w=nw, eps=c.eps, out_ids=out_ids, ws=ws,
-                                           logits=logits)
-            else:
-                ops.lm_head_argmax_w4(self.lm_head_q4, self.lm_head_e4, x, norm_w=nw, eps=c.eps, out_ids=out_ids, ws=ws, logits=logits)
-        elif proc is not None and fm:
-            ops.lm_head_argmax_fm_proc(self.lm_head_fm, h, c.vocab, proc, out_ids=out_ids, ws=ws, logits=logits, norm_eps=c.eps)
-        elif proc is not None:
-            ops.lm_head_argmax_proc(self.lm_head, h, proc, norm_w=self.norm, eps=c.eps, out_ids=out_ids, ws=ws, logits=logits)
+    def _decode_route(self, B: int) -> tuple:
+        """(layer route, its norm mode, head route, its norm mode) of a B-row decode step: keys of ROUTES and NORM_* values. Read at
+        the top of every step from the engine's settings and the row ranges as they are at that moment.
+        Layers: weight_dtype "fp8" / "mxfp4" engines stream the bytes row-major up to FP8_MAX_ROWS / MXFP4_MAX_ROWS rows (the norm fused
+        while the rows fit the kernel's LDS budget, else in a launch of its own); batched_weight_stream engines above that, up to
+        *_FM_MAX_ROWS rows, the same bytes in fragment-major order (csrc/gemv_qfm.hip; a quantised matrix cannot carry the norm);
+        everything else is bf16 -- fragment-major from FM_MIN_BATCH rows of an engine with the copies, which carry the norm's
+        weight, else row-major, whose GEMV fuses the norm for up to 4 rows.
+        Head: lm_head_dtype "fp8" / "mxfp4" engines stream its bytes up to LM_HEAD_*_MAX_ROWS rows (csrc/lm_head_wq.hip), everything
+        else is the bf16 route of that row count -- whatever the layers take."""
+        H = self.cfg.hidden
+        fm = self.fm_batch and B >= self.FM_MIN_BATCH
+        q = QUANT.get(self.weight_dtype)
+        if q and B <= min(getattr(self, q.rows), getattr(ops, q.op_rows)):
+            layer = (self.weight_dtype, NORM_ARG if getattr(ops, q.norm_fits)(B, H) else NORM_LAUNCH)
+        elif q and self.batched_weight_stream and B <= min(getattr(self, q.fm_rows), ops.QFM_MAX_ROWS):
+            layer = (self.weight_dtype + "_fm", NORM_LAUNCH)
         elif fm:
-            ops.lm_head_argmax_fm(self.lm_head_fm, h, c.vocab, out_ids=out_ids, ws=ws, logits=logits, norm_eps=c.eps)
+            layer = ("bf16_fm", NORM_FOLDED)
         else:
-            ops.lm_head_argmax(self.lm_head, h, norm_w=self.norm, eps=c.eps, out_ids=out_ids, ws=ws, logits=logits)
+            layer = ("bf16", NORM_ARG if B < 5 else NORM_LAUNCH)
+        q = QUANT.get(self.lm_head_dtype)
+        if q and B <= min(getattr(self, q.head_rows), ops.LM_HEAD_Q_MAX_ROWS):
+            head = (self.lm_head_dtype, NORM_ARG if getattr(ops, q.norm_fits)(B, H) else NORM_LAUNCH)
+        else:
+            head = ("bf16_fm", NORM_FOLDED) if fm else ("bf16", NORM_ARG)
+        return layer + head
+
+    def _lm_head_step(self, st: dict, h: torch.Tensor, out_ids: torch.Tensor, logits: Optional[torch.Tensor], proc: Optional[dict],
+                      head: Sequence[str]):
+        """The lm_head launch of a decode step: final norm + lm_head + arg-max (through `proc` when given) of the residual stream h
+        into out_ids, raw logits into `logits` when given, on head = (route, norm mode) of `_decode_route`."""
+        c, (name, norm) = self.cfg, head
+        route = ROUTES[name]
+        if route.fm:
+            args, kw = (h, c.vocab), dict(norm_eps=c.eps)
+        elif norm == NORM_LAUNCH:   # (a hidden size beyond the kernel's LDS budget)
+            args, kw = (ops.rmsnorm(h, self.norm, c.eps, out=st["xn"]),), dict(eps=c.eps)
+        else:
+            args, kw = (h,), dict(norm_w=self.norm, eps=c.eps)
+        if proc is not None:
+            args += (proc,)
+        getattr(ops, route.head if proc is None else route.head_proc)(
+            *(getattr(self, "lm_head" + s) for s in route.suffixes), *args, out_ids=out_ids, ws=st["lm_ws"], logits=logits, **kw)
 
     def _sample_step(self, st: dict):
         """Behind the raw-logits lm_head of a sampling step (graph-capturable, no host sync): st["next_ids"] = one draw per row from

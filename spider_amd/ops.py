@@ -279,6 +279,38 @@ def gemv_swiglu(W_gate_up, x, norm_w=None, eps=0.0, out=None):
     return out
 
 
+def _wq_plain(sym, chk, Wq, scale, x, bias, res, norm_w, eps, out, name):
+    """the body of gemv_w8 / gemv_w4: chk = the format's checker (-> K, B), sym = its kernel"""
+    K, B = chk(Wq, scale, x, name)
+    N = Wq.shape[0]
+    for t, n, cnt in ((bias, "bias", N), (res, "res", B * N), (norm_w, "norm_w", K)):
+        if t is not None:
+            _chk(t, BF16, n)
+            assert t.numel() == cnt, f"{n}: expected {cnt} elements"
+    if out is None:
+        out = torch.empty(B, N, dtype=BF16, device=x.device)
+    _chk(out, BF16, "out")
+    assert out.numel() == B * N
+    _lib.call(sym, _p(Wq), _p(scale), _p(x), _p(out), _p(bias), _p(res), _p(norm_w), float(eps), B, N, K, _stream())
+    return out
+
+
+def _wq_swiglu(sym, chk, Wq_gate_up, scale, x, norm_w, eps, out, name):
+    """the body of gemv_swiglu_w8 / gemv_swiglu_w4"""
+    K, B = chk(Wq_gate_up, scale, x, name)
+    I = Wq_gate_up.shape[0] // 2
+    assert Wq_gate_up.shape[0] == 2 * I
+    if norm_w is not None:
+        _chk(norm_w, BF16, "norm_w")
+        assert norm_w.numel() == K
+    if out is None:
+        out = torch.empty(B, I, dtype=BF16, device=x.device)
+    _chk(out, BF16, "out")
+    assert out.numel() == B * I
+    _lib.call(sym, _p(Wq_gate_up), _p(scale), _p(x), _p(out), _p(norm_w), float(eps), B, I, K, _stream())
+    return out
+
+
 FP8 = torch.float8_e4m3fn      # OCP e4m3fn (448 = 0x7e), the FP8 of gfx950 -- not MI300's e4m3fnuz
 W8_LDS_MAX_DEFAULT = 160 * 1024 - 256  # bytes of staged activations per block (csrc/wq_common.hpp: WQ_LDS_HW_LIMIT)
 W8_MAX_ROWS = 4                # rows the weight-only FP8 GEMVs exist for
@@ -305,34 +337,12 @@ def gemv_w8(Wq, scale, x, bias=None, res=None, norm_w=None, eps=0.0, out=None):
     """`gemv` on weight-only FP8: Wq [N, K] float8_e4m3fn, scale [N] fp32 per weight row (llm.quantize_fp8_rows);
     out[b,n] = scale[n] * sum_k xin[b,k] f32(Wq[n,k]) (+bias) (+res), the fp32 sum scaled once after the reduction. 1 <= B <= 4,
     K % 16 == 0."""
-    K, B = _chk_w8(Wq, scale, x, "Wq")
-    N = Wq.shape[0]
-    for t, n, cnt in ((bias, "bias", N), (res, "res", B * N), (norm_w, "norm_w", K)):
-        if t is not None:
-            _chk(t, BF16, n)
-            assert t.numel() == cnt, f"{n}: expected {cnt} elements"
-    if out is None:
-        out = torch.empty(B, N, dtype=BF16, device=x.device)
-    _chk(out, BF16, "out")
-    assert out.numel() == B * N
-    _lib.call("spider_gemv_w8", _p(Wq), _p(scale), _p(x), _p(out), _p(bias), _p(res), _p(norm_w), float(eps), B, N, K, _stream())
-    return out
+    return _wq_plain("spider_gemv_w8", _chk_w8, Wq, scale, x, bias, res, norm_w, eps, out, "Wq")
 
 
 def gemv_swiglu_w8(Wq_gate_up, scale, x, norm_w=None, eps=0.0, out=None):
     """`gemv_swiglu` on weight-only FP8: Wq_gate_up [2 I, K] = [gate rows | up rows], scale [2 I]. 1 <= B <= 4, K % 16 == 0."""
-    K, B = _chk_w8(Wq_gate_up, scale, x, "Wq_gate_up")
-    I = Wq_gate_up.shape[0] // 2
-    assert Wq_gate_up.shape[0] == 2 * I
-    if norm_w is not None:
-        _chk(norm_w, BF16, "norm_w")
-        assert norm_w.numel() == K
-    if out is None:
-        out = torch.empty(B, I, dtype=BF16, device=x.device)
-    _chk(out, BF16, "out")
-    assert out.numel() == B * I
-    _lib.call("spider_gemv_swiglu_w8", _p(Wq_gate_up), _p(scale), _p(x), _p(out), _p(norm_w), float(eps), B, I, K, _stream())
-    return out
+    return _wq_swiglu("spider_gemv_swiglu_w8", _chk_w8, Wq_gate_up, scale, x, norm_w, eps, out, "Wq_gate_up")
 
 
 W4_LDS_MAX_DEFAULT = 160 * 1024 - 256  # bytes of staged activations per block (csrc/wq_common.hpp: WQ_LDS_HW_LIMIT)
@@ -364,35 +374,13 @@ def gemv_w4(blocks, scales, x, bias=None, res=None, norm_w=None, eps=0.0, out=No
     """`gemv` on weight-only MXFP4 (llm.quantize_mxfp4): blocks [N, K / 2] uint8, two e2m1 codes per byte, low nibble first;
     scales [N, K / 32] uint8, E8M0, bytes 1..254. out[b,n] = sum_k xin[b,k] W_eff[n,k] (+bias) (+res) with
     W_eff[n,k] = e2m1(code) * 2^(scales[n, k / 32] - 127), the scale applied inside the conversion. 1 <= B <= 4, K % 32 == 0."""
-    K, B = _chk_w4(blocks, scales, x, "blocks")
-    N = blocks.shape[0]
-    for t, n, cnt in ((bias, "bias", N), (res, "res", B * N), (norm_w, "norm_w", K)):
-        if t is not None:
-            _chk(t, BF16, n)
-            assert t.numel() == cnt, f"{n}: expected {cnt} elements"
-    if out is None:
-        out = torch.empty(B, N, dtype=BF16, device=x.device)
-    _chk(out, BF16, "out")
-    assert out.numel() == B * N
-    _lib.call("spider_gemv_w4", _p(blocks), _p(scales), _p(x), _p(out), _p(bias), _p(res), _p(norm_w), float(eps), B, N, K, _stream())
-    return out
+    return _wq_plain("spider_gemv_w4", _chk_w4, blocks, scales, x, bias, res, norm_w, eps, out, "blocks")
 
 
 def gemv_swiglu_w4(blocks_gate_up, scales, x, norm_w=None, eps=0.0, out=None):
     """`gemv_swiglu` on weight-only MXFP4: blocks_gate_up [2 I, K / 2] = [gate rows | up rows], scales [2 I, K / 32].
     1 <= B <= 4, K % 32 == 0."""
-    K, B = _chk_w4(blocks_gate_up, scales, x, "blocks_gate_up")
-    I = blocks_gate_up.shape[0] // 2
-    assert blocks_gate_up.shape[0] == 2 * I
-    if norm_w is not None:
-        _chk(norm_w, BF16, "norm_w")
-        assert norm_w.numel() == K
-    if out is None:
-        out = torch.empty(B, I, dtype=BF16, device=x.device)
-    _chk(out, BF16, "out")
-    assert out.numel() == B * I
-    _lib.call("spider_gemv_swiglu_w4", _p(blocks_gate_up), _p(scales), _p(x), _p(out), _p(norm_w), float(eps), B, I, K, _stream())
-    return out
+    return _wq_swiglu("spider_gemv_swiglu_w4", _chk_w4, blocks_gate_up, scales, x, norm_w, eps, out, "blocks_gate_up")
 
 
 def repack_fm16(W: torch.Tensor, norm_w: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -576,18 +564,24 @@ def gemv_swiglu_fm_w8(qfm, scale, x, out=None):
     return _qfm_swiglu("spider_gemv_swiglu_fm_w8", qfm, scale, x, out, "qfm_gate_up", 8)
 
 
+def _lm_head_bufs(x, B, V, out_ids, ws):
+    """ids and workspaces of the bf16 lm_head_argmax* calls, allocated where missing -> (out_ids, ws, entries a workspace needs)"""
+    n = B * lm_head_nparts(V)
+    if ws is None:
+        ws = (torch.empty(n, dtype=torch.float32, device=x.device), torch.empty(n, dtype=torch.int32, device=x.device))
+    if out_ids is None:
+        out_ids = torch.empty(B, dtype=torch.int32, device=x.device)
+    return out_ids, ws, n
+
+
 def lm_head_argmax_fm(Wfm, x, V, out_ids=None, logits=None, ws=None, norm_eps=None):
     """Greedy argmax of x @ W^T on the fragment-major lm_head copy; 1 <= B <= 16. x normalised, or (norm_eps given, Wfm =
     repack_fm16(W, norm_w)) the un-normalised last hidden state."""
     _chk(Wfm, BF16, "Wfm"); _chk(x, BF16, "x")
     K = Wfm.shape[1] * 64
     B = x.numel() // K
-    npart = lm_head_nparts(V)
-    if ws is None:
-        ws = (torch.empty(B * npart, dtype=torch.float32, device=x.device), torch.empty(B * npart, dtype=torch.int32, device=x.device))
-    assert ws[0].numel() >= B * npart and ws[1].numel() >= B * npart
-    if out_ids is None:
-        out_ids = torch.empty(B, dtype=torch.int32, device=x.device)
+    out_ids, ws, n = _lm_head_bufs(x, B, V, out_ids, ws)
+    assert ws[0].numel() >= n and ws[1].numel() >= n
     _lib.call("spider_lm_head_argmax_fm_bf16", _p(Wfm), _p(x), _p(out_ids), _p(logits), _p(ws[0]), _p(ws[1]), B, V, K,
               int(norm_eps is not None), float(norm_eps or 0.0), _stream())
     return out_ids
@@ -601,12 +595,7 @@ def lm_head_argmax(W, x, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=Non
     _chk(W, BF16, "W"); _chk(x, BF16, "x")
     V, K = W.shape
     B = x.numel() // K
-    npart = lm_head_nparts(V)
-    if ws is None:
-        ws = (torch.empty(B * npart, dtype=torch.float32, device=x.device),
-              torch.empty(B * npart, dtype=torch.int32, device=x.device))
-    if out_ids is None:
-        out_ids = torch.empty(B, dtype=torch.int32, device=x.device)
+    out_ids, ws, _ = _lm_head_bufs(x, B, V, out_ids, ws)
     _lib.call("spider_lm_head_argmax_bf16", _p(W), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
               _p(ws[0]), _p(ws[1]), B, V, K, _stream())
     return out_ids
@@ -636,15 +625,10 @@ def lm_head_argmax_proc(W, x, proc: dict, norm_w=None, eps=0.0, out_ids=None, lo
     _chk(W, BF16, "W"); _chk(x, BF16, "x")
     V, K = W.shape
     B = x.numel() // K
-    npart = lm_head_nparts(V)
-    if ws is None:
-        ws = (torch.empty(B * npart, dtype=torch.float32, device=x.device),
-              torch.empty(B * npart, dtype=torch.int32, device=x.device))
-    assert ws[0].numel() >= B * npart and ws[1].numel() >= B * npart
+    out_ids, ws, n = _lm_head_bufs(x, B, V, out_ids, ws)
+    assert ws[0].numel() >= n and ws[1].numel() >= n
     if logits is not None:
         assert logits.numel() == B * V
-    if out_ids is None:
-        out_ids = torch.empty(B, dtype=torch.int32, device=x.device)
     _lib.call("spider_lm_head_argmax_proc_bf16", _p(W), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
               _p(ws[0]), _p(ws[1]), *_proc_args(proc, B, V), B, V, K, _stream())
     return out_ids
@@ -656,14 +640,10 @@ def lm_head_argmax_fm_proc(Wfm, x, V, proc: dict, out_ids=None, logits=None, ws=
     K = Wfm.shape[1] * 64
     B = x.numel() // K
     assert x.shape[-1] == K and Wfm.shape[0] == (V + 15) // 16
-    npart = lm_head_nparts(V)
-    if ws is None:
-        ws = (torch.empty(B * npart, dtype=torch.float32, device=x.device), torch.empty(B * npart, dtype=torch.int32, device=x.device))
-    assert ws[0].numel() >= B * npart and ws[1].numel() >= B * npart
+    out_ids, ws, n = _lm_head_bufs(x, B, V, out_ids, ws)
+    assert ws[0].numel() >= n and ws[1].numel() >= n
     if logits is not None:
         assert logits.numel() == B * V
-    if out_ids is None:
-        out_ids = torch.empty(B, dtype=torch.int32, device=x.device)
     _lib.call("spider_lm_head_argmax_fm_proc_bf16", _p(Wfm), _p(x), _p(out_ids), _p(logits), _p(ws[0]), _p(ws[1]),
               *_proc_args(proc, B, V), B, V, K, int(norm_eps is not None), float(norm_eps or 0.0), _stream())
     return out_ids
@@ -698,49 +678,42 @@ def _lm_head_q_bufs(name, x, B, V, K, norm_w, out_ids, logits, ws):
     return out_ids, ws
 
 
+def _lm_head_q(sym, q, scale, x, proc, norm_w, eps, out_ids, logits, ws):
+    """the body of lm_head_argmax[_proc]_w8 / _w4: sym = the kernel, "spider_" + the wrapper's name; proc None: the plain form"""
+    if sym.endswith("_w8"):
+        K, B = _chk_w8(q, scale, x, "q")
+        if K % 16:
+            raise ValueError(f"q: K = {K} has to be a multiple of 16 (16 e4m3 weights per 16-byte load)")
+    else:
+        K, B = _chk_w4(q, scale, x, "blocks")
+    V = q.shape[0]
+    out_ids, ws = _lm_head_q_bufs(sym[len("spider_"):], x, B, V, K, norm_w, out_ids, logits, ws)
+    _lib.call(sym, _p(q), _p(scale), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits), _p(ws[0]), _p(ws[1]),
+              *(() if proc is None else _proc_args(proc, B, V)), B, V, K, _stream())
+    return out_ids
+
+
 def lm_head_argmax_w8(q, scale, x, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=None):
     """`lm_head_argmax` on a weight-only FP8 head (llm.quantize_fp8_rows): q [V, K] float8_e4m3fn, scale [V] fp32; the fp32 sum is
     scaled once after the reduction. 1 <= B <= 4, K % 16 == 0; the fused norm needs w8_norm_fits(B, K)."""
-    K, B = _chk_w8(q, scale, x, "q")
-    if K % 16:
-        raise ValueError(f"q: K = {K} has to be a multiple of 16 (16 e4m3 weights per 16-byte load)")
-    out_ids, ws = _lm_head_q_bufs("lm_head_argmax_w8", x, B, q.shape[0], K, norm_w, out_ids, logits, ws)
-    _lib.call("spider_lm_head_argmax_w8", _p(q), _p(scale), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
-              _p(ws[0]), _p(ws[1]), B, q.shape[0], K, _stream())
-    return out_ids
+    return _lm_head_q("spider_lm_head_argmax_w8", q, scale, x, None, norm_w, eps, out_ids, logits, ws)
 
 
 def lm_head_argmax_proc_w8(q, scale, x, proc: dict, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=None):
     """lm_head_argmax_w8 with the logits processors of lm_head_argmax_proc in the arg-max epilogue; `logits` stay raw."""
-    K, B = _chk_w8(q, scale, x, "q")
-    if K % 16:
-        raise ValueError(f"q: K = {K} has to be a multiple of 16 (16 e4m3 weights per 16-byte load)")
-    V = q.shape[0]
-    out_ids, ws = _lm_head_q_bufs("lm_head_argmax_proc_w8", x, B, V, K, norm_w, out_ids, logits, ws)
-    _lib.call("spider_lm_head_argmax_proc_w8", _p(q), _p(scale), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
-              _p(ws[0]), _p(ws[1]), *_proc_args(proc, B, V), B, V, K, _stream())
-    return out_ids
+    return _lm_head_q("spider_lm_head_argmax_proc_w8", q, scale, x, proc, norm_w, eps, out_ids, logits, ws)
 
 
 def lm_head_argmax_w4(blocks, scales, x, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=None):
     """`lm_head_argmax` on a weight-only MXFP4 head (llm.quantize_mxfp4): blocks [V, K / 2] uint8, scales [V, K / 32] uint8 (E8M0,
     bytes 1..254), the block scale applied inside the conversion. 1 <= B <= 4, K % 32 == 0; the fused norm needs
     w4_norm_fits(B, K)."""
-    K, B = _chk_w4(blocks, scales, x, "blocks")
-    out_ids, ws = _lm_head_q_bufs("lm_head_argmax_w4", x, B, blocks.shape[0], K, norm_w, out_ids, logits, ws)
-    _lib.call("spider_lm_head_argmax_w4", _p(blocks), _p(scales), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
-              _p(ws[0]), _p(ws[1]), B, blocks.shape[0], K, _stream())
-    return out_ids
+    return _lm_head_q("spider_lm_head_argmax_w4", blocks, scales, x, None, norm_w, eps, out_ids, logits, ws)
 
 
 def lm_head_argmax_proc_w4(blocks, scales, x, proc: dict, norm_w=None, eps=0.0, out_ids=None, logits=None, ws=None):
     """lm_head_argmax_w4 with the logits processors of lm_head_argmax_proc in the arg-max epilogue; `logits` stay raw."""
-    K, B = _chk_w4(blocks, scales, x, "blocks")
-    V = blocks.shape[0]
-    out_ids, ws = _lm_head_q_bufs("lm_head_argmax_proc_w4", x, B, V, K, norm_w, out_ids, logits, ws)
-    _lib.call("spider_lm_head_argmax_proc_w4", _p(blocks), _p(scales), _p(x), _p(norm_w), float(eps), _p(out_ids), _p(logits),
-              _p(ws[0]), _p(ws[1]), *_proc_args(proc, B, V), B, V, K, _stream())
-    return out_ids
+    return _lm_head_q("spider_lm_head_argmax_proc_w4", blocks, scales, x, proc, norm_w, eps, out_ids, logits, ws)
 
 
 def decode_advance_seen(next_ids, cur_ids, pos, slot, kv_end, seen, V, hist=None, n_hist=None):
